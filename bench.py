@@ -18,8 +18,20 @@ micro-batches execute as ONE forward/backward over the whole 2048-sample batch,
 whose loss is scaled so the gradient equals the reference's sum of per-micro-batch
 means (tests/test_trainer.py checks this, also for uneven chunks).  That is the
 MI355X-first choice - 288 GB of HBM hold the activations, and 8192-token GEMMs
-fill a 256-CU chip only ~60%.  The reference's own 32 x 64 schedule is measured in
-the same process and reported under ``reference_schedule`` (``--ref-steps``).
+fill a 256-CU chip only ~60%.
+
+A plain run does only what the headline figure needs: set up, warm up, time the
+steps, write ``--dump-outputs`` if asked, print the result line.  ``--full`` adds
+the measurements that take runs of their own: the reference's own 32 x 64
+schedule in the same process (``reference_schedule``, ``--ref-steps``), the
+one-GPU projection (``--project``), the N > 1 comm probe (``comm_probe``) and the
+node's xGMI ``topology``.
+
+``--dump-outputs DIR`` writes what the last timed step left a caller with, as
+``DIR/<name>.npy``: a fixed seeded sample of the updated parameters and of each
+EMA copy (float32), and the logged loss terms and gradient norm (float64, the
+logger's mean over the steps since its last dump).  Inputs (weights, data order,
+noise) are seeded, so two builds can be compared output for output.
 
 Reported ``value`` is the whole-job aggregate: optimizer steps/s x N
 (= samples/s / 2048), so it scales with N under weak scaling; rank-local
@@ -83,6 +95,12 @@ def parse():
     ap.add_argument("--data-workers", type=int, default=2)
     ap.add_argument("--log-interval", type=int, default=20)
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the reference 32 x 64 schedule "
+                         "(--ref-*), --project, the N > 1 comm probe and the xGMI topology query")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy: seeded "
+                         "samples of the parameters and EMA copies, the logged loss terms and gradient norm")
     ap.add_argument("--project", default="",
                     help="N = 1 only, after the measurements: a one-GPU PROJECTION of the W > 1 data plane. "
                          "';'-separated specs W,busbw_GBps[,cus[,lat_us[,bucket_cap_mb,first_bucket_mb]]] ('/' "
@@ -98,7 +116,12 @@ def parse():
     ap.add_argument("--comm-probe", type=int, default=1,
                     help="N > 1: after the timed runs, time the full gradient reduction and the "
                          "process group's all-reduce at 1-128 MB (reported under comm_probe)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.project and not a.full:
+        ap.error("--project needs --full")
+    return a
 
 
 def topology():
@@ -250,6 +273,35 @@ def project(a, loop, one_step, timed, exec_used, base):
             "base_ms_per_step": base, "reps": a.project_reps, "runs": out}
 
 
+DUMP_SAMPLE = 1 << 21  # elements kept of each dumped parameter set (8 MB as float32)
+DUMP_SCALARS = ("loss", "mse", "nll", "decoder_nll", "grad_norm")
+
+
+def collect_outputs(loop, kvs):
+    """What the last timed step left a caller with, as host numpy arrays (--dump-outputs):
+    the updated parameters and each EMA copy (model.parameters() order, flattened; past
+    DUMP_SAMPLE elements a fixed seeded sample of them) and the logged scalars.  Every rank
+    calls it (a sharded optimizer gathers its EMA shards)."""
+    import numpy as np
+    import torch
+
+    def sample(params):
+        flat = torch.cat([p.detach().reshape(-1).float() for p in params])
+        if flat.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(0)  # its own generator: the run's RNG streams stay put
+            idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        return flat.cpu().numpy().astype(np.float32)
+
+    out = {"params": sample(list(loop.model.parameters()))}
+    for rate, params in zip(loop.ema_rate, loop.ema_params):
+        out[f"ema_{rate}"] = sample(params)
+    for k in DUMP_SCALARS:
+        if k in kvs:
+            out[k] = np.asarray([float(kvs[k])], dtype=np.float64)
+    return out
+
+
 def main():
     a = parse()
     import torch
@@ -301,11 +353,13 @@ def main():
         diffusion, sampler = create_diffusion_from_config(diffusion_steps=2000, noise_schedule="sqrt")
         loop = DiffusionTrainLoop(diffusion=diffusion, schedule_sampler=sampler, **kw)
 
+    last_kvs = {}  # the logger's latest dump (--dump-outputs reads the scalars from it)
+
     def one_step():
         batch = next(loop.data)
         loop.run_step(batch)
         if loop.step % loop.log_interval == 0:
-            logger.dumpkvs()
+            last_kvs.update(logger.dumpkvs())
         loop.step += 1
 
     def sync():
@@ -336,6 +390,11 @@ def main():
 
     exec_used = loop.exec_microbatch
 
+    outputs = None
+    if a.dump_outputs:  # taken now: --full goes on training
+        last_kvs.update(logger.dumpkvs())
+        outputs = collect_outputs(loop, last_kvs)
+
     host = [0.0]  # host time to enqueue the last timed window (before its closing sync)
 
     def timed(n):
@@ -353,7 +412,7 @@ def main():
         return e
 
     ref_sched = None
-    if a.ref_steps > 0 and not ref and exec_used != a.microbatch:
+    if a.full and a.ref_steps > 0 and not ref and exec_used != a.microbatch:
         # the reference's own schedule: one fwd/bwd per 64-sample micro-batch, no_sync on
         # all but the last (same model, optimizer state and process)
         loop._exec_auto = False
@@ -402,7 +461,7 @@ def main():
             ref_sched["windows_diag"] = diag
 
     projection = None
-    if a.project and world == 1 and engine == "native" and dev.type == "cuda":
+    if a.full and a.project and world == 1 and engine == "native" and dev.type == "cuda":
         base = {"fused": round(elapsed / a.steps * 1e3, 3),
                 "reference": ref_sched["ms_per_step"] if ref_sched else None}
         projection = project(a, loop, one_step, timed, exec_used, base)
@@ -487,7 +546,7 @@ def main():
                                               if engine == "native" else world),
                     "rank_ms_per_step_min": round(rank_ms[0], 3),
                     "rank_ms_per_step_max": round(rank_ms[1], 3)}
-    if world > 1 and a.comm_probe:
+    if a.full and world > 1 and a.comm_probe:
         try:  # diagnostics only: never cost the measured line
             out["comm_probe"] = comm_probe(loop, engine, dev, sync)
         except Exception as e:  # noqa: BLE001
@@ -510,8 +569,13 @@ def main():
         if nat is not None and hasattr(nat, "comm_stream") and nat.direct():
             out["streams"]["handles"]["comm"] = hex(nat.comm_stream())
     if rank == 0:
-        out["topology"] = topology()
+        out["topology"] = topology() if a.full else None
     if rank == 0:
+        if outputs is not None:
+            import numpy as np
+            os.makedirs(a.dump_outputs, exist_ok=True)
+            for name, arr in outputs.items():
+                np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
         line = json.dumps(out)
         print(line, flush=True)
         if a.json_out:

@@ -13,6 +13,16 @@ def pytest_configure(config):
     config.addinivalue_line("markers", "slow: multi-process or long-running test")
 
 
+@pytest.fixture(autouse=True)
+def _fresh_quartile_sums():
+    """The trainer's quartile sums are process-wide until the next logger dump: a test that
+    ends without one must not hand them (on its device) to the next test's trainer."""
+    trainer = sys.modules.get("utils.trainer")
+    if trainer is not None:
+        trainer._QuartileAcc.store.clear()
+    yield
+
+
 def pytest_collection_modifyitems(config, items):
     try:
         import torch

@@ -16,7 +16,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _run(tmp_path, extra_env=None, extra_args=()):
     env = dict(os.environ)
     env.pop("LOCAL_RANK", None)
-    env.update(OMP_NUM_THREADS="1", PYTHONPATH=ROOT, **(extra_env or {}))
+    # CPU ranks also where a GPU is present (two RCCL ranks cannot share one device)
+    env.update(OMP_NUM_THREADS="1", PYTHONPATH=ROOT, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1",
+               **(extra_env or {}))
     cmd = [sys.executable, "-m", "run.train", "--distributed", "--nproc_per_node", "2",
            "--master_addr", "127.0.0.1", "--master_port", str(find_free_port()),
            "--config_json", os.path.join(ROOT, "configs", "tiny_mlp_cpu.json"),
@@ -69,12 +71,13 @@ def test_bench_contract_two_ranks_gloo():
     (tiny config on CPU ranks): rank 0 prints ONE JSON line with the whole-job value."""
     import json
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, OMP_NUM_THREADS="2")
+    # CPU ranks also where a GPU is present (two RCCL ranks cannot share one device)
+    env = dict(os.environ, OMP_NUM_THREADS="2", HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(find_free_port()),
                           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
                           "--config-name", "tiny", "--batch-size", "8", "--microbatch", "4", "--seq-len", "64",
-                          "--data-workers", "0"],
+                          "--data-workers", "0", "--full"],
                          capture_output=True, text=True, timeout=300, env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -95,3 +98,37 @@ def test_bench_contract_two_ranks_gloo():
     bt = d["config"]["bucket_tune"]
     assert bt["cap_mb"] in [r["mb"] for r in bt["sweep"]] and bt["first_mb"] <= bt["cap_mb"]
     assert all(r["busbw_GBps"] > 0 for r in bt["sweep"])
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain bench.py run (tiny config, one CPU process) times --steps steps and nothing else:
+    no reference schedule, comm probe or topology query (those are --full), and
+    --dump-outputs writes the last step's parameters, EMA copies and logged scalars as
+    float32 / float64 .npy files."""
+    import json
+
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, OMP_NUM_THREADS="2")
+    dump = tmp_path / "out"
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3",
+                          "--warmup", "1", "--config-name", "tiny", "--batch-size", "8", "--microbatch", "4",
+                          "--seq-len", "64", "--data-workers", "0", "--dump-outputs", str(dump)],
+                         capture_output=True, text=True, timeout=300, env=env, cwd=root)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]
+    assert d["reference_schedule"] is None and d["topology"] is None
+    assert "comm_probe" not in d and "projection" not in d
+    files = {p.name: np.load(p) for p in dump.iterdir()}
+    assert {"params.npy", "ema_0.5.npy", "ema_0.9.npy", "ema_0.99.npy", "loss.npy", "grad_norm.npy"} <= set(files)
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in files.values())
+    assert files["params.npy"].size == min(d["config"]["params"], 1 << 21)
+    assert files["ema_0.5.npy"].shape == files["params.npy"].shape
+    # the EMA copies trail the parameters they average
+    assert not np.array_equal(files["ema_0.99.npy"], files["params.npy"])
+    assert sum(v.nbytes for v in files.values()) <= 64 << 20

@@ -81,8 +81,9 @@ def main(steps):
             name = f[1]
             args = f[2].split(",") if len(f) > 2 and f[2] else []
             js = os.path.join(OUT, name + ".json")
-            _run([sys.executable, "-u", "bench.py", "--json-out", js] + args, os.path.join(OUT, name + ".log"), 600,
-                 env)
+            # --full: this step also reports the reference schedule
+            _run([sys.executable, "-u", "bench.py", "--full", "--json-out", js] + args,
+                 os.path.join(OUT, name + ".log"), 600, env)
             with open(js) as fh:
                 d = json.load(fh)
             print(f"[run] {name}: {d['ms_per_step']} ms/step; reference schedule "
@@ -127,7 +128,8 @@ def main(steps):
             for i in range(reps):
                 for v in (a, b):
                     js = os.path.join(OUT, f"ab_{var}_{v}_{i}.json")
-                    _run([sys.executable, "-u", "bench.py", "--steps", "10", "--warmup", "3", "--json-out", js] + args,
+                    _run([sys.executable, "-u", "bench.py", "--full", "--steps", "10", "--warmup", "3", "--json-out", js]
+                         + args,
                          os.path.join(OUT, f"ab_{var}_{v}_{i}.log"), 600, dict(env, **{var: v}))
                     line = f"{var}={v} rep {i}: {_bench_ms(js)} ms/step"
                     print("[run] " + line, flush=True)
