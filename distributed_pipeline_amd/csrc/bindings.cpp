@@ -149,6 +149,45 @@ static std::vector<at::Tensor> lxent_fwd_dx(const at::Tensor& x, const at::Tenso
   return {loss, lse, dxu};
 }
 
+// ---- fused linear + arg-max (decoding) -------------------------------------------
+static void check_argmax_w(const at::Tensor& W) {
+  CHECK_DEV(W); CHECK_BF16(W); CHECK_CONTIG(W);
+  TORCH_CHECK(W.dim() == 2 && W.size(0) > 0, "W [V,E] with V > 0");
+  TORCH_CHECK(W.size(1) == 128 || W.size(1) == 256, "linear_argmax: E must be 128 or 256");
+}
+
+static std::vector<at::Tensor> linear_argmax(const at::Tensor& x, const at::Tensor& W,
+                                             c10::optional<at::Tensor> c) {
+  check_argmax_w(W);
+  CHECK_DEV(x); CHECK_BF16(x); CHECK_CONTIG(x);
+  TORCH_CHECK(x.dim() == 2 && x.size(1) == W.size(1), "x [N,E], W [V,E]");
+  TORCH_CHECK(x.device() == W.device(), "x and W must be on one device");
+  const float* cp = nullptr;
+  if (c.has_value() && c->defined()) {
+    CHECK_DEV((*c)); CHECK_F32((*c)); CHECK_CONTIG((*c));
+    TORCH_CHECK(c->numel() == W.size(0) && c->device() == W.device(), "c [V] fp32 on W's device");
+    cp = c->data_ptr<float>();
+  }
+  const c10::DeviceGuard guard(x.device());
+  const int N = (int)x.size(0), V = (int)W.size(0), E = (int)x.size(1);
+  at::Tensor idx = at::empty({N}, x.options().dtype(at::kLong));
+  at::Tensor best = at::empty({N}, x.options().dtype(at::kFloat));
+  if (N == 0) return {idx, best};
+  const int64_t wsn = dpa::linear_argmax_workspace_floats(N, V);
+  at::Tensor ws = at::empty({wsn}, x.options().dtype(at::kFloat));
+  dpa::launch_linear_argmax(bf_ptr(x), bf_ptr(W), cp, N, V, E, idx.data_ptr<int64_t>(),
+                            best.data_ptr<float>(), wsn ? ws.data_ptr<float>() : nullptr, cur_stream());
+  return {idx, best};
+}
+
+static at::Tensor row_half_sqnorm(const at::Tensor& W) {
+  check_argmax_w(W);
+  const c10::DeviceGuard guard(W.device());
+  at::Tensor c = at::empty({W.size(0)}, W.options().dtype(at::kFloat));
+  dpa::launch_row_half_sqnorm(bf_ptr(W), (int)W.size(0), (int)W.size(1), c.data_ptr<float>(), cur_stream());
+  return c;
+}
+
 static void emb_grad(const at::Tensor& ids, const at::Tensor& dy, at::Tensor& dW);
 
 // onehot_scatter: the dW kernel leaves out the target one-hot (softmax only) and it is added
@@ -1233,6 +1272,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "128-row tiles of the persistent GEMMs: 0 off, 1 auto (when they finish sooner), 2 always, -1 default");
   m.def("set_gemmp_dynamic", &dpa::set_gemmp_dynamic,
         "dynamic per-XCD tile queues for the persistent GEMMs (on for world > 1; env DPA_GEMMP_DYNAMIC wins)");
+  m.def("linear_argmax", &linear_argmax,
+        "row-wise arg-max of x W^T + c without the scores -> (idx int64, best fp32); ties: lowest index",
+        py::arg("x"), py::arg("W"), py::arg("c") = py::none());
+  m.def("row_half_sqnorm", &row_half_sqnorm, "c[v] = -1/2 ||W[v]||^2 in fp32 from a bf16 W");
   m.def("lxent_fwd", &lxent_fwd, "fused linear + cross-entropy forward -> (loss, lse)");
   m.def("lxent_fwd_dx", &lxent_fwd_dx,
         "fused linear-CE forward + unscaled input gradient -> (loss, lse, dxu fp32 [N, E])");

@@ -57,6 +57,15 @@ struct TransposeBatch {
 bool launch_transpose_bf16_batch(const TransposeBatch& d, hipStream_t s);
 void launch_cast_f32(const uint16_t* src, float* dst, int64_t n, hipStream_t s);  // n % 4 == 0
 
+// ---- linear_argmax.hip (fused linear + arg-max: decoding) -----------------------
+// idx[t] = argmax_v (x[t] . W[v] + c[v]) (ties: lowest v), best[t] = that score; c fp32 or null;
+// ws: linear_argmax_workspace_floats(N, V) floats of scratch (0: this shape is not split)
+int64_t linear_argmax_workspace_floats(int N, int V);
+void launch_linear_argmax(const uint16_t* x, const uint16_t* W, const float* c, int N, int V, int E,
+                          int64_t* idx, float* best, float* ws, hipStream_t s);
+// c[v] = -1/2 ||W[v]||^2 (fp32), E in {128, 256}
+void launch_row_half_sqnorm(const uint16_t* W, int V, int E, float* c, hipStream_t s);
+
 // ---- xent.hip (fused linear + cross-entropy) ----------------------------------
 int64_t lxent_workspace_floats(int N, int V);
 // forward + unscaled input gradient in one sweep: dxu[t] = softmax_t . W - W[target_t] (fp32)

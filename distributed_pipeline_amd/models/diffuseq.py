@@ -85,6 +85,31 @@ class TransformerNetModel(nn.Module):
         dt = self.compute_dtype
         return ops.linear_cross_entropy(x.to(dt), self.lm_head.weight, self.lm_head.bias, ids)
 
+    # -- decoding (no [N, V] tensor either) -----------------------------------
+    def rounding_offsets(self):
+        """``-1/2 ||e_v||^2`` (fp32 [V]) of the embedding table as :meth:`nearest_tokens` reads it;
+        a sampler computes it once and passes it to every rounding call."""
+        return ops.row_half_sqnorm(self.word_embedding.weight, self.compute_dtype)
+
+    def nearest_tokens(self, x, c=None):
+        """ids of the word embedding nearest to each row of x ([..., E] in the diffusion space
+        ``emb_scale_factor * e_v``; ties: lowest id).  ``c``: :meth:`rounding_offsets`."""
+        s = self.emb_scale_factor
+        xs = x.detach() if s == 1.0 else x.detach() / s  # argmin_v |x - s e_v| = argmin_v |x / s - e_v|, s > 0
+        ids, _ = ops.linear_argmax(xs.to(self.compute_dtype), self.word_embedding.weight, nearest=True, c=c)
+        return ids
+
+    def round_to_embeds(self, x, c=None):
+        """x with every row replaced by its nearest word embedding (fp32, diffusion space):
+        DiffuSeq's clamping trick, the ``denoised_fn`` of the reverse process."""
+        return self.get_embeds(self.nearest_tokens(x, c))
+
+    def decode_tokens(self, x):
+        """Arg-max of the tied rounding head's logits (bias included; ties: lowest id), i.e.
+        ``get_logits(x).argmax(-1)`` without the logits."""
+        ids, _ = ops.linear_argmax(x.detach().to(self.compute_dtype), self.lm_head.weight, self.lm_head.bias)
+        return ids
+
     # -- forward ------------------------------------------------------------
     def forward(self, x, timesteps):
         dt = self.compute_dtype

@@ -137,11 +137,14 @@ class GaussianDiffusion:
         return self.q_posterior_mean(pred_x0, x, t), self._extract(name, t, x.dim()), pred_x0
 
     @torch.no_grad()
-    def p_sample(self, model, x, t, mask=None, x_start=None, clip_denoised=False, denoised_fn=None):
+    def p_sample(self, model, x, t, mask=None, x_start=None, clip_denoised=False, denoised_fn=None,
+                 generator=None):
         """One ancestral step x_t -> x_{t-1}; positions with mask == 0 (the source
-        sequence) are kept at x_start (DiffuSeq partial noising)."""
+        sequence) are kept at x_start (DiffuSeq partial noising).  The noise comes from
+        ``generator`` (a ``torch.Generator`` on x's device) when given."""
         mean, logvar, pred_x0 = self.p_mean_variance(model, x, t, clip_denoised, denoised_fn)
-        noise = torch.randn_like(x)
+        noise = (torch.randn_like(x) if generator is None
+                 else torch.randn(x.shape, dtype=x.dtype, device=x.device, generator=generator))
         nonzero = (t != 0).float().view(-1, *([1] * (x.dim() - 1)))
         sample = mean + nonzero * torch.exp(0.5 * logvar) * noise
         if mask is not None and x_start is not None:
@@ -150,15 +153,43 @@ class GaussianDiffusion:
 
     @torch.no_grad()
     def p_sample_loop(self, model, shape, noise=None, mask=None, x_start=None, clip_denoised=False,
-                      denoised_fn=None, device=None):
-        """Sample x_0 from T steps of the reverse process (returns the final sample)."""
-        x = torch.randn(*shape, device=device) if noise is None else noise
+                      denoised_fn=None, device=None, *, clamp_step=None, generator=None):
+        """Sample x_0 from T steps of the reverse process (returns the final sample).
+
+        clamp_step: apply ``denoised_fn`` only at the reverse steps t <= clamp_step (DiffuSeq's
+        ``--clamp_step``; None: at every step).  generator: source of the start noise (unless
+        ``noise`` is given) and of every step's noise, so a seed reproduces the sample."""
+        x = torch.randn(*shape, device=device, generator=generator) if noise is None else noise
         if mask is not None and x_start is not None:
             x = torch.where(mask.unsqueeze(-1) == 0, x_start, x)
         for i in reversed(range(self.num_timesteps)):
             t = torch.full((shape[0],), i, dtype=torch.long, device=x.device)
-            x, _ = self.p_sample(model, x, t, mask, x_start, clip_denoised, denoised_fn)
+            fn = denoised_fn if (clamp_step is None or i <= clamp_step) else None
+            x, _ = self.p_sample(model, x, t, mask, x_start, clip_denoised, fn, generator=generator)
         return x
+
+    @torch.no_grad()
+    def sample_seq2seq(self, model, batch, *, clamp_step=None, generator=None):
+        """Decode the target half of ``batch`` (``input_ids`` [B, L]; ``input_mask`` 1 on the
+        target positions) with the reverse process, the source positions kept at their word
+        embeddings; every predicted x_0 (at the steps t <= clamp_step; None: all) is rounded to
+        its nearest word embedding.
+
+        -> {"tokens": [B, L] ids, the source positions copied from ``input_ids``;
+            "x0": [B, L, E] fp32, the final sample; "source_mask": [B, L] bool}"""
+        net = getattr(model, "module", model)
+        input_ids, input_mask = batch["input_ids"], batch["input_mask"]
+        x_start = net.get_embeds(input_ids)
+        c = net.rounding_offsets()  # once, not per step
+
+        def round_fn(x, t):
+            return net.round_to_embeds(x, c)
+
+        x0 = self.p_sample_loop(model, x_start.shape, mask=input_mask, x_start=x_start, denoised_fn=round_fn,
+                                device=x_start.device, clamp_step=clamp_step, generator=generator)
+        source = input_mask == 0
+        tokens = torch.where(source, input_ids, net.decode_tokens(x0))
+        return {"tokens": tokens, "x0": x0, "source_mask": source}
 
     # -- loss ---------------------------------------------------------------
     def training_losses(self, model, *args, **kwargs):

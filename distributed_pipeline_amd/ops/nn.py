@@ -1617,6 +1617,78 @@ def linear_cross_entropy(x, weight, bias, target):
 
 
 # --------------------------------------------------------------------------- #
+# Fused linear + arg-max (decoding: rounding to the nearest embedding, final tokens)
+# --------------------------------------------------------------------------- #
+
+# fp32 scores alive at once on the PyTorch path (tokens are chunked to stay under it)
+_ARGMAX_CHUNK_BYTES = 256 << 20
+
+
+def _argmax_native(x, w16):
+    return (x.dtype == torch.bfloat16 and w16.dtype == torch.bfloat16 and x.shape[-1] in (128, 256)
+            and native_ok(x, w16, kernel="linear_argmax"))
+
+
+def row_half_sqnorm(weight, dtype=None):
+    """c_v = -1/2 ||w_v||^2 in fp32, of ``weight`` as a ``dtype`` computation reads it (its bf16
+    shadow for bf16): the offsets that turn :func:`linear_argmax` into a nearest-row search."""
+    w = weight if dtype is None else shadow(weight, dtype)
+    if (w.dtype == torch.bfloat16 and w.dim() == 2 and w.shape[1] in (128, 256)
+            and native_ok(w, kernel="row_half_sqnorm")):
+        return get_ext().row_half_sqnorm(w.contiguous())
+    wf = w.detach().float()
+    return -0.5 * (wf * wf).sum(-1)
+
+
+def _linear_argmax_ref(x2, wf, c):
+    """The same formula in fp32 PyTorch, chunked over tokens.  Ties go to the lowest index (max
+    over the scores, then min over the matching indices: ``torch.argmax`` documents no tie
+    order); NaN scores never win, as in the kernel."""
+    N, V = x2.shape[0], wf.shape[0]
+    idx = torch.empty(N, dtype=torch.int64, device=x2.device)
+    best = torch.empty(N, dtype=torch.float32, device=x2.device)
+    rows = max(1, _ARGMAX_CHUNK_BYTES // (4 * V))
+    ar = torch.arange(V, dtype=torch.int32, device=x2.device)
+    for i in range(0, N, rows):
+        s = x2[i:i + rows].float() @ wf.t()
+        if c is not None:
+            s += c
+        s = torch.where(torch.isnan(s), float("-inf"), s)
+        m = s.amax(-1)
+        best[i:i + rows] = m
+        idx[i:i + rows] = torch.where(s == m.unsqueeze(-1), ar, V).amin(-1)
+    return idx, best
+
+
+def linear_argmax(x, weight, bias=None, *, nearest=False, c=None):
+    """Row-wise arg-max of ``x @ W^T + c`` without materialising the [N, V] scores.
+
+    x: [..., E]; weight: [V, E] -> (idx int64 [...], best fp32 [...]).  The offsets are ``c``
+    (fp32 [V]) when given, else ``-1/2 ||w_v||^2`` with ``nearest=True`` (the nearest row of W to
+    each x, DiffuSeq's rounding; ``bias`` is ignored), else ``bias``: the arg-max of the logits.
+    Equal scores resolve to the lowest index.  A caller that rounds repeatedly against one
+    weight computes ``c = row_half_sqnorm(weight, x.dtype)`` once and passes it.
+
+    bf16 on a HIP device with E in {128, 256}: csrc/linear_argmax.hip; anything else (CPU, fp32,
+    other E): the same formula in chunked fp32 PyTorch.
+    """
+    lead, E = x.shape[:-1], x.shape[-1]
+    x2 = x.detach().reshape(-1, E)
+    w = shadow(weight, x.dtype).detach()
+    if c is None:
+        if nearest:
+            c = row_half_sqnorm(w)
+        elif bias is not None:
+            c = bias.detach().float()
+    if _argmax_native(x2, w):
+        idx, best = get_ext().linear_argmax(x2.contiguous(), w.contiguous(),
+                                            None if c is None else c.float().contiguous())
+    else:
+        idx, best = _linear_argmax_ref(x2, w.float(), None if c is None else c.float())
+    return idx.view(lead), best.view(lead)
+
+
+# --------------------------------------------------------------------------- #
 # Embedding gather with fp32 weight grad
 # --------------------------------------------------------------------------- #
 

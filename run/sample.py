@@ -1,0 +1,149 @@
+"""
+Entry point: ``python -m run.sample --config_json cfg.json --model_path DIR --out_path out.jsonl``
+
+Decodes a dataset split with a trained DiffuSeq checkpoint (one process; one GPU, or the CPU):
+settings -> model + diffusion -> state dict -> ``eval()`` -> for each batch the reverse process
+with every predicted x0 rounded to its nearest word embedding
+(``GaussianDiffusion.sample_seq2seq``) -> one JSON line per sample with the ``source``,
+``reference`` and ``recover`` token ids (padding stripped), and their texts when ``data_dir`` holds
+a ``vocab.txt``.
+
+``--config_json`` takes the ``training_args.json`` of the training run as it is
+(config/sample.py).  A seed reproduces the output: the sampling noise comes from one generator
+seeded with ``seed``.
+"""
+import json
+import os
+import re
+
+from config.sample import SampleSettings
+
+
+def create_parser():
+    return SampleSettings.to_argparse(add_json=True)
+
+
+def find_checkpoint(model_path, use_ema=""):
+    """``model_path`` itself when it is a file; else the newest ``ema_<use_ema>_NNNNNN.pt``
+    (``use_ema`` set; rates compare as numbers) or ``model_NNNNNN.pt`` of that directory."""
+    if os.path.isfile(model_path):
+        return model_path
+    if not os.path.isdir(model_path):
+        raise FileNotFoundError(f"model_path {model_path!r} is neither a file nor a directory")
+    best = None
+    for name in os.listdir(model_path):
+        if use_ema:
+            m = re.fullmatch(r"ema_(.+)_(\d+)\.pt", name)
+            try:
+                ok = m is not None and float(m.group(1)) == float(use_ema)
+            except ValueError:
+                ok = False
+        else:
+            m = re.fullmatch(r"model_?(\d+)\.pt", name)
+            ok = m is not None
+        if ok and (best is None or int(m.groups()[-1]) > best[0]):
+            best = (int(m.groups()[-1]), name)
+    if best is None:
+        what = f"ema_{use_ema}_NNNNNN.pt" if use_ema else "model_NNNNNN.pt"
+        raise FileNotFoundError(f"no {what} in {model_path!r}")
+    return os.path.join(model_path, best[1])
+
+
+def load_vocab(data_dir):
+    """id -> token of ``{data_dir}/vocab.txt`` (the WordPiece file the dataset's tokenizer reads),
+    or None."""
+    path = os.path.join(data_dir, "vocab.txt")
+    if not os.path.exists(path):
+        return None
+    with open(path, encoding="utf-8") as f:
+        return [line.rstrip("\n") for line in f]
+
+
+def detokenize(ids, vocab):
+    words = []
+    for i in ids:
+        tok = vocab[i] if 0 <= i < len(vocab) else "[UNK]"
+        if tok.startswith("##") and words:
+            words[-1] += tok[2:]
+        else:
+            words.append(tok)
+    return " ".join(words)
+
+
+def split_sample(ids, mask, recovered, pad_id=0):
+    """(source, reference, recover) id lists of one sample: ``mask`` is 0 on the source and 1 on
+    the target and the padding after it; padding (trailing ``pad_id``) is stripped - from the
+    recovered target wherever the model put its first pad."""
+    n_src = int((mask == 0).sum())
+    source = ids[:n_src].tolist()
+    reference = ids[n_src:].tolist()
+    while reference and reference[-1] == pad_id:
+        reference.pop()
+    recover = recovered[n_src:].tolist()
+    if pad_id in recover:
+        recover = recover[:recover.index(pad_id)]
+    return source, reference, recover
+
+
+def main(namespace):
+    args: SampleSettings = SampleSettings.from_argparse(namespace)
+
+    import torch
+
+    from basic_utils import dist_util
+    from data import load_data_from_args
+    from data.dataset import PAD_ID
+    from utils.initialization import create_diffusion_from_config, create_model_from_config
+
+    if args.model != "diffuseq":
+        raise ValueError(f"run.sample decodes the diffuseq model, not {args.model!r}")
+    dev = torch.device("cuda:0") if torch.cuda.is_available() else torch.device("cpu")
+    if dev.type == "cuda":
+        torch.cuda.set_device(dev)
+
+    model = create_model_from_config(**args.dict())
+    diffusion, _ = create_diffusion_from_config(**args.dict())
+    ckpt = find_checkpoint(args.model_path, args.use_ema)
+    print(f"### loading {ckpt}")
+    model.load_state_dict(dist_util.load_state_dict(ckpt, map_location="cpu"))
+    model.to(dev).eval()
+    if args.precision == "bf16":
+        for p in model.parameters():  # frozen weights: one bf16 cast, not one per forward (ops.shadow)
+            p._dpa_shadow = p.detach().to(torch.bfloat16)
+
+    data = load_data_from_args(split=args.split, data_dir=args.data_dir, batch_size=args.batch_size,
+                               deterministic=True, loop=False, num_loader_proc=0,
+                               dataset=args.dataset, seq_len=args.seq_len, vocab_size=args.vocab_size,
+                               seed=args.seed, model=args.model)
+    vocab = load_vocab(args.data_dir)
+    out_path = args.out_path
+    if not out_path:
+        stem = os.path.splitext(os.path.basename(ckpt))[0]
+        out_path = os.path.join(os.path.dirname(os.path.abspath(ckpt)), f"samples_{stem}_seed{args.seed}.jsonl")
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(args.seed)
+    clamp_step = None if args.clamp_step < 0 else args.clamp_step
+    n = 0
+    with open(out_path, "w") as fout:
+        for b, batch in enumerate(data):
+            if b >= args.num_batches:
+                break
+            batch = {k: v.to(dev) for k, v in batch.items()}
+            out = diffusion.sample_seq2seq(model, batch, clamp_step=clamp_step, generator=gen)
+            ids, mask, rec = batch["input_ids"].cpu(), batch["input_mask"].cpu(), out["tokens"].cpu()
+            for i in range(ids.shape[0]):
+                src, ref, hyp = split_sample(ids[i], mask[i], rec[i], PAD_ID)
+                line = {"source": src, "reference": ref, "recover": hyp}
+                if vocab is not None:
+                    line.update(source_text=detokenize(src, vocab), reference_text=detokenize(ref, vocab),
+                                recover_text=detokenize(hyp, vocab))
+                fout.write(json.dumps(line) + "\n")
+                n += 1
+    print(f"### wrote {n} samples to {out_path}")
+    return out_path
+
+
+if __name__ == "__main__":
+    main(create_parser().parse_args())
