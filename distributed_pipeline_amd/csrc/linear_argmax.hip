@@ -7,8 +7,8 @@
 //   c = -1/2 ||W[v]||^2      -> the nearest word embedding of x[t] (DiffuSeq's clamping
 //                               trick: argmin_v ||x - W[v]||^2), row_half_sqnorm below.
 //
-// The [N, V] scores are never written.  The sweep is the forward of csrc/xent.hip: a
-// workgroup is 128 tokens and walks (a split of) the vocabulary in 64-row W tiles staged
+// The [N, V] scores are never written.  The sweep (csrc/vocab_sweep.h) is shared with the
+// forward of csrc/xent.hip: a workgroup is 128 tokens and walks (a split of) the vocabulary in 64-row W tiles staged
 // through the swizzled LDS image; S = W x^T puts the token on the MFMA lane and the
 // vocabulary in the accumulator registers, which start at c (fp32, never rounded to bf16:
 // ||W[v]||^2 at bf16 precision would move the arg-min).  Where xent.hip keeps an online
@@ -33,39 +33,9 @@
 #include "common.h"
 #include "launchers.h"
 #include "mfma.h"
+#include "vocab_sweep.h"
 
 namespace dpa {
-
-// W-tile staging (64 rows x E) into the swizzled LDS image, register-staged: the same image
-// as WTile of xent.hip (kept identical; the kernels of both files read it with lds_frag).
-template <int E, int NT>
-struct WTile {
-  static constexpr int CH = E / 8;             // 16-byte chunks per row
-  static constexpr int ROWB = E * 2;
-  static constexpr int PER = 64 * CH / NT;     // chunks per thread
-  uint4 r[PER];
-
-  __device__ __forceinline__ void load(const bf16_t* __restrict__ W, int v0, int V, int tid) {
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int c = tid + i * NT;
-      const int row = c / CH, ch = c % CH;
-      const int v = v0 + row;
-      if (v < V)
-        r[i] = *reinterpret_cast<const uint4*>(W + (int64_t)v * E + ch * 8);
-      else
-        r[i] = make_uint4(0, 0, 0, 0);
-    }
-  }
-  __device__ __forceinline__ void store(char* lds, int tid) const {
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int c = tid + i * NT;
-      const int row = c / CH, ch = c % CH;
-      *reinterpret_cast<uint4*>(lds + swz<ROWB>(row, ch)) = r[i];
-    }
-  }
-};
 
 // ---------------------------------------------------------------------------
 // Sweep
@@ -80,20 +50,13 @@ __global__ void __launch_bounds__(256) linear_argmax_kernel(
   char* wt = smem;
   float* ct = reinterpret_cast<float*>(smem + 64 * ROWB);
 
-  // xsplit > 1: vocabulary split s = blockIdx.x % xsplit, one per XCD (see lxent_fwd_kernel):
-  // every XCD sweeps only its 1/8 of W, which stays resident in that XCD's L2
-  const int split = xsplit > 1 ? (int)(blockIdx.x % xsplit) : (int)blockIdx.y;
-  const int tblk = xsplit > 1 ? (int)(blockIdx.x / xsplit) : (int)blockIdx.x;
-  const int nsplit = xsplit > 1 ? xsplit : (int)gridDim.y;
+  const auto [split, tblk, nsplit] = sweep_block(xsplit);
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, h = lane >> 5;
   const int t = tblk * 128 + w * 32 + (lane & 31);
   const bool tok_ok = t < N;
   bf16x8 xf[KS];
 #pragma unroll
-  for (int s = 0; s < KS; ++s) {
-    if (tok_ok) xf[s] = ld_frag(x + (int64_t)t * E + 16 * s + 8 * h);
-    else for (int j = 0; j < 8; ++j) xf[s][j] = 0;
-  }
+  for (int s = 0; s < KS; ++s) xf[s] = token_frag<E>(x, t, tok_ok, s, h);
 
   const int vbeg = split * v_per_split;  // < V: the launcher makes no empty split
   const int vend = min(V, vbeg + v_per_split);
@@ -104,10 +67,7 @@ __global__ void __launch_bounds__(256) linear_argmax_kernel(
   if (vbeg < vend) stage.load(W, vbeg, V, tid);
   for (int v0 = vbeg; v0 < vend; v0 += 64) {
     stage.store(wt, tid);
-    if (tid < 64) {
-      const int v = v0 + tid;
-      ct[tid] = (v < vend) ? (c ? c[v] : 0.f) : -INFINITY;
-    }
+    stage_offsets(ct, v0, vend, tid, [c](int v) { return c ? c[v] : 0.f; });
     __syncthreads();
     if (v0 + 64 < vend) stage.load(W, v0 + 64, V, tid);  // prefetch next tile behind the MFMAs
 
@@ -211,46 +171,29 @@ __global__ void __launch_bounds__(256) row_half_sqnorm_kernel(const bf16_t* __re
 // Vocabulary splits, chosen as launch_lxent_fwd chooses its own: enough workgroups to fill
 // the chip (1024), so from 1024 token blocks (N > 130944) one workgroup sweeps the whole
 // vocabulary; below that the split count is a multiple of 8 (one split per XCD).
-static void argmax_plan(int N, int V, int& Sx, int& vps) {
-  const int tb = (N + 127) / 128;
-  const int vchunks = (V + 63) / 64;
-  int S = (1024 + tb - 1) / tb;
-  if (S > vchunks) S = vchunks;
-  if (S > 1 && vchunks >= 8) S = (S + 7) / 8 * 8;
-  vps = ((vchunks + S - 1) / S) * 64;
-  Sx = (V + vps - 1) / vps;
-}
+static SweepPlan argmax_plan(int N, int V) { return sweep_plan(N, V, 1024, XcdRound::if_split); }
 
+// ws layout: Sx x N split maxima (float), Sx x N split indices (int)
 int64_t linear_argmax_workspace_floats(int N, int V) {
-  int Sx, vps;
-  argmax_plan(N, V, Sx, vps);
+  const int Sx = argmax_plan(N, V).Sx;
   return Sx > 1 ? 2 * (int64_t)Sx * N : 0;
-}
-
-template <int E>
-static void argmax_impl(const bf16_t* x, const bf16_t* W, const float* c, int N, int V, int64_t* idx,
-                        float* best, float* ws, hipStream_t st) {
-  const int tb = (N + 127) / 128;
-  int Sx, vps;
-  argmax_plan(N, V, Sx, vps);
-  float* pb = ws;
-  int* pi = reinterpret_cast<int*>(ws + (Sx > 1 ? (int64_t)Sx * N : 0));
-  if (Sx == 8)  // one split per XCD: 1-D grid, split = blockIdx % 8
-    hipLaunchKernelGGL(linear_argmax_kernel<E>, dim3(tb * 8), dim3(256), 0, st, x, W, c, N, V, vps, idx,
-                       best, pb, pi, 8);
-  else
-    hipLaunchKernelGGL(linear_argmax_kernel<E>, dim3(tb, Sx), dim3(256), 0, st, x, W, c, N, V, vps, idx,
-                       best, pb, pi, 0);
-  if (Sx > 1)
-    hipLaunchKernelGGL(linear_argmax_combine_kernel, dim3((N + 255) / 256), dim3(256), 0, st,
-                       (const float*)pb, (const int*)pi, N, Sx, idx, best);
 }
 
 // ws: linear_argmax_workspace_floats(N, V) floats of scratch (the splits' (best, idx) partials)
 void launch_linear_argmax(const uint16_t* x, const uint16_t* W, const float* c, int N, int V, int E,
                           int64_t* idx, float* best, float* ws, hipStream_t s) {
-  if (E == 128) argmax_impl<128>(x, W, c, N, V, idx, best, ws, s);
-  else argmax_impl<256>(x, W, c, N, V, idx, best, ws, s);
+  const SweepPlan p = argmax_plan(N, V);
+  float* pb = ws;
+  int* pi = reinterpret_cast<int*>(ws + (p.Sx > 1 ? (int64_t)p.Sx * N : 0));
+  const bool per_xcd = p.Sx == 8;  // one split per XCD: 1-D grid, split = blockIdx % 8
+  const dim3 grid = per_xcd ? dim3(p.tb * 8) : dim3(p.tb, p.Sx);
+  for_head_width(E, [&](auto e) {
+    hipLaunchKernelGGL(linear_argmax_kernel<e()>, grid, dim3(256), 0, s, x, W, c, N, V, p.vps, idx, best, pb, pi,
+                       per_xcd ? 8 : 0);
+  });
+  if (p.Sx > 1)
+    hipLaunchKernelGGL(linear_argmax_combine_kernel, dim3((N + 255) / 256), dim3(256), 0, s, pb, pi, N, p.Sx,
+                       idx, best);
 }
 
 void launch_row_half_sqnorm(const uint16_t* W, int V, int E, float* c, hipStream_t s) {

@@ -27,42 +27,16 @@
 #include "common.h"
 #include "launchers.h"
 #include "mfma.h"
+#include "vocab_sweep.h"
 
 namespace dpa {
 
-static constexpr float LOG2E = 1.4426950408889634f;
 static constexpr float LN2 = 0.6931471805599453f;
 
-// ---------------------------------------------------------------------------
-// W-tile staging (64 rows x E) into a swizzled LDS image, register-staged.
-// ---------------------------------------------------------------------------
-template <int E, int NT>
-struct WTile {
-  static constexpr int CH = E / 8;             // 16-byte chunks per row
-  static constexpr int ROWB = E * 2;
-  static constexpr int PER = 64 * CH / NT;     // chunks per thread
-  uint4 r[PER];
-
-  __device__ __forceinline__ void load(const bf16_t* __restrict__ W, int v0, int V, int tid) {
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int c = tid + i * NT;
-      const int row = c / CH, ch = c % CH;
-      const int v = v0 + row;
-      if (v < V)
-        r[i] = *reinterpret_cast<const uint4*>(W + (int64_t)v * E + ch * 8);
-      else
-        r[i] = make_uint4(0, 0, 0, 0);
-    }
-  }
-  __device__ __forceinline__ void store(char* lds, int tid) const {
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int c = tid + i * NT;
-      const int row = c / CH, ch = c % CH;
-      *reinterpret_cast<uint4*>(lds + swz<ROWB>(row, ch)) = r[i];
-    }
-  }
+// per-row offset of the loss kernels' logit tiles (stage_offsets): the bf16 bias, 0 without one
+struct BiasOffset {
+  const bf16_t* bias;
+  __device__ __forceinline__ float operator()(int v) const { return bias ? bf2f(bias[v]) : 0.f; }
 };
 
 __device__ __forceinline__ float sel16(const f32x16& a, int i) {
@@ -86,21 +60,13 @@ __global__ void __launch_bounds__(256) lxent_fwd_kernel(
   char* wt = smem;
   float* bt = reinterpret_cast<float*>(smem + 64 * ROWB);
 
-  // xsplit > 1: vocabulary split s = blockIdx.x % xsplit, i.e. (with the round-robin
-  // workgroup -> XCD dispatch) every XCD sweeps only its 1/8 of W, which then stays
-  // resident in that XCD's L2 instead of streaming all of W from the MALL per workgroup
-  const int split = xsplit > 1 ? (int)(blockIdx.x % xsplit) : (int)blockIdx.y;
-  const int tblk = xsplit > 1 ? (int)(blockIdx.x / xsplit) : (int)blockIdx.x;
-  const int nsplit = xsplit > 1 ? xsplit : (int)gridDim.y;
+  const auto [split, tblk, nsplit] = sweep_block(xsplit);
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, h = lane >> 5;
   const int t = tblk * 128 + w * 32 + (lane & 31);
   const bool tok_ok = t < N;
   bf16x8 xf[KS];
 #pragma unroll
-  for (int s = 0; s < KS; ++s) {
-    if (tok_ok) xf[s] = ld_frag(x + (int64_t)t * E + 16 * s + 8 * h);
-    else for (int j = 0; j < 8; ++j) xf[s][j] = 0;
-  }
+  for (int s = 0; s < KS; ++s) xf[s] = token_frag<E>(x, t, tok_ok, s, h);
   const int64_t tg = tok_ok ? target[t] : -1;
 
   const int vbeg = split * v_per_split;
@@ -125,10 +91,7 @@ __global__ void __launch_bounds__(256) lxent_fwd_kernel(
   if (vbeg < vend) stage.load(W, vbeg, V, tid);
   for (int v0 = vbeg; v0 < vend; v0 += 64) {
     stage.store(wt, tid);
-    if (tid < 64) {
-      const int v = v0 + tid;
-      bt[tid] = (v < vend) ? (bias ? bf2f(bias[v]) : 0.f) : -INFINITY;
-    }
+    stage_offsets(bt, v0, vend, tid, BiasOffset{bias});
     __syncthreads();
     if (v0 + 64 < vend) stage.load(W, v0 + 64, V, tid);  // prefetch next tile behind the MFMAs
 
@@ -225,10 +188,7 @@ __global__ void __launch_bounds__(256) lxent_dx_kernel(
   const bool tok_ok = t < N;
   bf16x8 xf[KS];
 #pragma unroll
-  for (int s = 0; s < KS; ++s) {
-    if (tok_ok) xf[s] = ld_frag(x + (int64_t)t * E + 16 * s + 8 * h);
-    else for (int j = 0; j < 8; ++j) xf[s][j] = 0;
-  }
+  for (int s = 0; s < KS; ++s) xf[s] = token_frag<E>(x, t, tok_ok, s, h);
   const int64_t tg = tok_ok ? target[t] : -1;
   const bool valid = tok_ok && tg >= 0 && tg < V;
   const float g = valid ? dloss[t] : 0.f;
@@ -244,10 +204,7 @@ __global__ void __launch_bounds__(256) lxent_dx_kernel(
   if (vbeg < vend) stage.load(W, vbeg, V, tid);
   for (int v0 = vbeg; v0 < vend; v0 += 64) {
     stage.store(wt, tid);
-    if (tid < 64) {
-      const int v = v0 + tid;
-      bt[tid] = (v < vend) ? (bias ? bf2f(bias[v]) : 0.f) : -INFINITY;
-    }
+    stage_offsets(bt, v0, vend, tid, BiasOffset{bias});
     __syncthreads();
     if (v0 + 64 < vend) stage.load(W, v0 + 64, V, tid);
 
@@ -328,10 +285,7 @@ __global__ void __launch_bounds__(256, E == 128 ? 2 : 1) lxent_fwd_dx_kernel(
   const bool tok_ok = t < N;
   bf16x8 xf[KS];
 #pragma unroll
-  for (int s = 0; s < KS; ++s) {
-    if (tok_ok) xf[s] = ld_frag(x + (int64_t)t * E + 16 * s + 8 * h);
-    else for (int j = 0; j < 8; ++j) xf[s][j] = 0;
-  }
+  for (int s = 0; s < KS; ++s) xf[s] = token_frag<E>(x, t, tok_ok, s, h);
   const int64_t tg = tok_ok ? target[t] : -1;
   f32x16 dacc[KT];
 #pragma unroll
@@ -342,10 +296,7 @@ __global__ void __launch_bounds__(256, E == 128 ? 2 : 1) lxent_fwd_dx_kernel(
   stage.load(W, v_lo, V, tid);
   for (int v0 = v_lo; v0 < v_hi; v0 += 64) {
     stage.store(wt, tid);
-    if (tid < 64) {
-      const int v = v0 + tid;
-      bt[tid] = (v < v_hi) ? (bias ? bf2f(bias[v]) : 0.f) : -INFINITY;
-    }
+    stage_offsets(bt, v0, v_hi, tid, BiasOffset{bias});
     __syncthreads();
     if (v0 + 64 < v_hi) stage.load(W, v0 + 64, V, tid);  // prefetch behind the MFMAs
 
@@ -669,132 +620,76 @@ __global__ void __launch_bounds__(256) f32_to_bf16_kernel(const float* __restric
 // ---------------------------------------------------------------------------
 // Launchers
 // ---------------------------------------------------------------------------
-static int pick_splits(int blocks, int chunks, int target_wgs) {
-  int s = (target_wgs + blocks - 1) / blocks;
-  if (s < 1) s = 1;
-  if (s > chunks) s = chunks;
-  return s;
-}
+// Vocabulary splits of the forward: at least 8 (one per XCD, see sweep_block) once the
+// vocabulary has 8 x 64 rows, more when there are too few token blocks to fill the chip.
+static SweepPlan fwd_plan(int N, int V) { return sweep_plan(N, V, 1024, XcdRound::always); }
 
-// vocabulary splits of the forward: at least 8 (one per XCD, see the kernel) once the
-// vocabulary has 8 x 64 rows, more when there are too few token blocks to fill the chip
-static int fwd_splits(int N, int V) {
-  const int tb = (N + 127) / 128;
-  const int vchunks = (V + 63) / 64;
-  int S = pick_splits(tb, vchunks, 1024);
-  constexpr int xs = 8;
-  if (xs > 1 && vchunks >= xs) S = (S + xs - 1) / xs * xs;
-  return S;
-}
+// ws layout: Sx x N split maxima, Sx x N split sums, N target logits
+int64_t lxent_workspace_floats(int N, int V) { return (2 * (int64_t)fwd_plan(N, V).Sx + 1) * N + 64; }
 
-template <int E>
-static void fwd_impl(const bf16_t* x, const bf16_t* W, const bf16_t* b, const int64_t* tgt, int N,
-                     int V, float* loss, float* lse, float* ws, hipStream_t st) {
-  const int tb = (N + 127) / 128;
-  const int vchunks = (V + 63) / 64;
-  const int S = fwd_splits(N, V);
-  const int vps = ((vchunks + S - 1) / S) * 64;
-  const int Sx = (V + vps - 1) / vps;
+void launch_lxent_fwd(const uint16_t* x, const uint16_t* W, const uint16_t* b, const int64_t* tgt,
+                      int N, int V, int E, float* loss, float* lse, float* ws, hipStream_t s) {
+  const SweepPlan p = fwd_plan(N, V);
   float* pm = ws;
-  float* ps = ws + (int64_t)Sx * N;
-  float* tl = ws + 2 * (int64_t)Sx * N;
-  if (Sx == 8)  // one split per XCD: 1-D grid, split = blockIdx % 8
-    hipLaunchKernelGGL(lxent_fwd_kernel<E>, dim3(tb * 8), dim3(256), 0, st, x, W, b, tgt, N, V, vps, loss,
-                       lse, pm, ps, tl, 8);
-  else
-    hipLaunchKernelGGL(lxent_fwd_kernel<E>, dim3(tb, Sx), dim3(256), 0, st, x, W, b, tgt, N, V, vps, loss,
-                       lse, pm, ps, tl, 0);
-  if (Sx > 1)
-    hipLaunchKernelGGL(lxent_combine_kernel, dim3((N + 255) / 256), dim3(256), 0, st, pm, ps, tl,
-                       tgt, N, V, Sx, loss, lse);
+  float* ps = ws + (int64_t)p.Sx * N;
+  float* tl = ws + 2 * (int64_t)p.Sx * N;
+  const bool per_xcd = p.Sx == 8;  // one split per XCD: 1-D grid, split = blockIdx % 8
+  const dim3 grid = per_xcd ? dim3(p.tb * 8) : dim3(p.tb, p.Sx);
+  for_head_width(E, [&](auto e) {
+    hipLaunchKernelGGL(lxent_fwd_kernel<e()>, grid, dim3(256), 0, s, x, W, b, tgt, N, V, p.vps, loss, lse, pm,
+                       ps, tl, per_xcd ? 8 : 0);
+  });
+  if (p.Sx > 1)
+    hipLaunchKernelGGL(lxent_combine_kernel, dim3((N + 255) / 256), dim3(256), 0, s, pm, ps, tl,
+                       tgt, N, V, p.Sx, loss, lse);
 }
 
 // Vocabulary splits of the fused forward + dx: one block per 128 tokens sweeps the whole
 // vocabulary, so below ~3 blocks per CU (a reference-schedule micro-batch: 8192 tokens =
-// 64 blocks for 256 CUs) the vocabulary is split over gridDim.y and merged afterwards.
-static void fwd_dx_plan(int N, int V, int& S, int& vps) {
-  const int tb = (N + 127) / 128, vchunks = (V + 63) / 64;
-  S = 1;
-  vps = vchunks * 64;
-  if (tb >= 768) return;
-  int want = (768 + tb - 1) / tb;
-  if (want > vchunks) want = vchunks;
-  if (want < 2) return;
-  vps = ((vchunks + want - 1) / want) * 64;
-  S = (V + vps - 1) / vps;
-}
+// 64 blocks for 256 CUs; no split from 768 blocks) the vocabulary is split over gridDim.y
+// and merged afterwards.
+static SweepPlan fwd_dx_plan(int N, int V) { return sweep_plan(N, V, 768, XcdRound::none); }
 
+// ws layout: S x N maxima, S x N sums, S x N target logits, S x N x E unnormalised u
 int64_t lxent_fwd_dx_workspace_floats(int N, int V, int E) {
-  int S, vps;
-  fwd_dx_plan(N, V, S, vps);
+  const int S = fwd_dx_plan(N, V).Sx;
   return S > 1 ? (int64_t)S * N * (3 + E) : 0;
-}
-
-template <int E>
-static void fwd_dx_impl(const bf16_t* x, const bf16_t* W, const bf16_t* b, const int64_t* tgt, int N, int V,
-                        float* loss, float* lse, float* dxu, float* ws, hipStream_t s) {
-  const unsigned tb = (unsigned)((N + 127) / 128);
-  int S, vps;
-  fwd_dx_plan(N, V, S, vps);
-  if (S > 1 && ws != nullptr) {
-    hipLaunchKernelGGL(lxent_fwd_dx_kernel<E>, dim3(tb, S), dim3(256), 0, s, x, W, b, tgt, N, V, loss, lse,
-                       dxu, vps, ws);
-    const int64_t n = (int64_t)N * E;
-    hipLaunchKernelGGL(lxent_fwd_dx_combine_kernel<E>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ws,
-                       S, W, tgt, N, V, loss, lse, dxu);
-  } else {
-    hipLaunchKernelGGL(lxent_fwd_dx_kernel<E>, dim3(tb), dim3(256), 0, s, x, W, b, tgt, N, V, loss, lse, dxu,
-                       V, nullptr);
-  }
 }
 
 void launch_lxent_fwd_dx(const uint16_t* x, const uint16_t* W, const uint16_t* b, const int64_t* tgt,
                          int N, int V, int E, float* loss, float* lse, float* dxu, hipStream_t s, float* ws) {
-  if (E == 128)
-    fwd_dx_impl<128>((const bf16_t*)x, (const bf16_t*)W, (const bf16_t*)b, tgt, N, V, loss, lse, dxu, ws, s);
-  else
-    fwd_dx_impl<256>((const bf16_t*)x, (const bf16_t*)W, (const bf16_t*)b, tgt, N, V, loss, lse, dxu, ws, s);
-}
-
-int64_t lxent_workspace_floats(int N, int V) {
-  const int vchunks = (V + 63) / 64;
-  const int S = fwd_splits(N, V);
-  const int vps = ((vchunks + S - 1) / S) * 64;
-  const int Sx = (V + vps - 1) / vps;
-  return (2 * (int64_t)Sx + 1) * N + 64;
-}
-
-void launch_lxent_fwd(const uint16_t* x, const uint16_t* W, const uint16_t* b, const int64_t* tgt,
-                      int N, int V, int E, float* loss, float* lse, float* ws, hipStream_t s) {
-  if (E == 128) fwd_impl<128>(x, W, b, tgt, N, V, loss, lse, ws, s);
-  else fwd_impl<256>(x, W, b, tgt, N, V, loss, lse, ws, s);
-}
-
-template <int E>
-static void dx_impl(const bf16_t* x, const bf16_t* W, const bf16_t* b, const int64_t* tgt,
-                    const float* lse, const float* dl, int N, int V, uint16_t* dx, float* dx_acc,
-                    hipStream_t st) {
-  const int tb = (N + 127) / 128;
-  const int vchunks = (V + 63) / 64;
-  const int S = dx_acc ? pick_splits(tb, vchunks, 1024) : 1;
-  const int vps = ((vchunks + S - 1) / S) * 64;
-  const int Sx = (V + vps - 1) / vps;
-  hipLaunchKernelGGL(lxent_dx_kernel<E>, dim3(tb, Sx), dim3(256), 0, st, x, W, b, tgt, lse, dl, N, V,
-                     vps, (bf16_t*)dx, Sx > 1 ? dx_acc : nullptr);
-  if (Sx > 1) {
-    const int64_t n = (int64_t)N * E;
-    hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)((n / 4 + 255) / 256 + 1)), dim3(256), 0,
-                       st, dx_acc, (bf16_t*)dx, n);
-  }
+  const SweepPlan p = fwd_dx_plan(N, V);
+  for_head_width(E, [&](auto e) {
+    if (p.Sx > 1 && ws != nullptr) {
+      hipLaunchKernelGGL(lxent_fwd_dx_kernel<e()>, dim3(p.tb, p.Sx), dim3(256), 0, s, x, W, b, tgt, N, V, loss,
+                         lse, dxu, p.vps, ws);
+      const int64_t n = (int64_t)N * E;
+      hipLaunchKernelGGL(lxent_fwd_dx_combine_kernel<e()>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ws,
+                         p.Sx, W, tgt, N, V, loss, lse, dxu);
+    } else {
+      hipLaunchKernelGGL(lxent_fwd_dx_kernel<e()>, dim3(p.tb), dim3(256), 0, s, x, W, b, tgt, N, V, loss, lse,
+                         dxu, V, nullptr);
+    }
+  });
 }
 
 bool lxent_dx_needs_acc(int N) { return (N + 127) / 128 < 512; }
 
+// dx_acc (fp32 [N][E], zeroed): the vocabulary splits add into it; without it one block
+// sweeps the whole vocabulary
 void launch_lxent_dx(const uint16_t* x, const uint16_t* W, const uint16_t* b, const int64_t* tgt,
                      const float* lse, const float* dloss, int N, int V, int E, uint16_t* dx,
                      float* dx_acc, hipStream_t s) {
-  if (E == 128) dx_impl<128>(x, W, b, tgt, lse, dloss, N, V, dx, dx_acc, s);
-  else dx_impl<256>(x, W, b, tgt, lse, dloss, N, V, dx, dx_acc, s);
+  const SweepPlan p = sweep_plan(N, V, dx_acc ? 1024 : 0, XcdRound::none);
+  for_head_width(E, [&](auto e) {
+    hipLaunchKernelGGL(lxent_dx_kernel<e()>, dim3(p.tb, p.Sx), dim3(256), 0, s, x, W, b, tgt, lse, dloss, N, V,
+                       p.vps, dx, p.Sx > 1 ? dx_acc : nullptr);
+  });
+  if (p.Sx > 1) {
+    const int64_t n = (int64_t)N * E;
+    hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)((n / 4 + 255) / 256 + 1)), dim3(256), 0,
+                       s, dx_acc, dx, n);
+  }
 }
 
 // token splits of the weight-gradient kernel (enough workgroups to fill the chip)

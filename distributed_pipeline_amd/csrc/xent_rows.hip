@@ -18,8 +18,6 @@
 
 namespace dpa {
 
-static constexpr float XR_LOG2E = 1.4426950408889634f;
-
 __device__ __forceinline__ void xr_unpack8(const uint4& r, float* v) {
   const uint32_t w[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
@@ -42,17 +40,14 @@ __device__ __forceinline__ uint4 xr_pack8(const float* v) {
 __device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2) {
   const float M = fmaxf(m, m2);
   if (M == -INFINITY) return;  // both still empty
-  s = s * fexp2((m - M) * XR_LOG2E) + s2 * fexp2((m2 - M) * XR_LOG2E);
+  s = s * fexp2((m - M) * LOG2E) + s2 * fexp2((m2 - M) * LOG2E);
   m = M;
 }
 
-__global__ void __launch_bounds__(256) xent_rows_fwd_kernel(const bf16_t* __restrict__ lg, int64_t ld,
-                                                            int V, const int64_t* __restrict__ tgt,
-                                                            float* __restrict__ loss,
-                                                            float* __restrict__ lse_out) {
+// Log-sum-exp of the row's V columns: online (max, sum) per thread, merged across the wave by
+// shuffles and across the 4 waves through LDS.  256 threads; the result is thread 0's alone.
+__device__ __forceinline__ float xr_row_lse(const bf16_t* row, int V) {
   __shared__ float red_m[4], red_s[4];
-  const int64_t r = blockIdx.x;
-  const bf16_t* row = lg + r * ld;
   float m = -INFINITY, s = 0.f;
   for (int c = threadIdx.x * 8; c < V; c += 256 * 8) {
     float v[8];
@@ -66,8 +61,8 @@ __global__ void __launch_bounds__(256) xent_rows_fwd_kernel(const bf16_t* __rest
     const float mn = fmaxf(m, tm);  // finite: column c < V is valid
     float add = 0.f;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) add += fexp2((v[k] - mn) * XR_LOG2E);
-    s = s * fexp2((m - mn) * XR_LOG2E) + add;
+    for (int k = 0; k < 8; ++k) add += fexp2((v[k] - mn) * LOG2E);
+    s = s * fexp2((m - mn) * LOG2E) + add;
     m = mn;
   }
 #pragma unroll
@@ -78,11 +73,24 @@ __global__ void __launch_bounds__(256) xent_rows_fwd_kernel(const bf16_t* __rest
     red_s[w] = s;
   }
   __syncthreads();
+  float l = 0.f;
   if (threadIdx.x == 0) {
     float M = red_m[0], S = red_s[0];
 #pragma unroll
     for (int i = 1; i < 4; ++i) lse_merge(M, S, red_m[i], red_s[i]);
-    const float l = M + logf(S);
+    l = M + logf(S);
+  }
+  return l;
+}
+
+__global__ void __launch_bounds__(256) xent_rows_fwd_kernel(const bf16_t* __restrict__ lg, int64_t ld,
+                                                            int V, const int64_t* __restrict__ tgt,
+                                                            float* __restrict__ loss,
+                                                            float* __restrict__ lse_out) {
+  const int64_t r = blockIdx.x;
+  const bf16_t* row = lg + r * ld;
+  const float l = xr_row_lse(row, V);
+  if (threadIdx.x == 0) {
     const int64_t t = tgt[r];
     const bool valid = t >= 0 && t < V;
     loss[r] = valid ? l - bf2f(row[t]) : 0.f;
@@ -99,14 +107,14 @@ __global__ void __launch_bounds__(256) xent_rows_bwd_kernel(bf16_t* __restrict__
   const int64_t t = tgt[r];
   const bool valid = t >= 0 && t < V;
   const float g = valid ? dloss[r] : 0.f;
-  const float l2 = lse[r] * XR_LOG2E;
+  const float l2 = lse[r] * LOG2E;
   for (int c = threadIdx.x * 8; c < ld; c += 256 * 8) {
     float v[8];
     xr_unpack8(*reinterpret_cast<const uint4*>(row + c), v);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const int col = c + k;
-      float p = col < V ? g * fexp2(fmaf(v[k], XR_LOG2E, -l2)) : 0.f;
+      float p = col < V ? g * fexp2(fmaf(v[k], LOG2E, -l2)) : 0.f;
       if (col == t) p -= g;
       v[k] = p;
     }
@@ -126,44 +134,16 @@ __global__ void __launch_bounds__(256) xent_rows_fwd_grad_kernel(bf16_t* __restr
                                                                 const int64_t* __restrict__ tgt,
                                                                 float* __restrict__ loss,
                                                                 float* __restrict__ lse_out) {
-  __shared__ float red_m[4], red_s[4], bcast;
+  __shared__ float bcast;
   const int64_t r = blockIdx.x;
   bf16_t* row = lg + r * ld;
   const int64_t t = tgt[r];
   const bool valid = t >= 0 && t < V;
-  float m = -INFINITY, s = 0.f;
-  for (int c = threadIdx.x * 8; c < V; c += 256 * 8) {
-    float v[8];
-    xr_unpack8(*reinterpret_cast<const uint4*>(row + c), v);
-    float tm = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      if (c + k >= V) v[k] = -INFINITY;
-      tm = fmaxf(tm, v[k]);
-    }
-    const float mn = fmaxf(m, tm);
-    float add = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) add += fexp2((v[k] - mn) * XR_LOG2E);
-    s = s * fexp2((m - mn) * XR_LOG2E) + add;
-    m = mn;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) lse_merge(m, s, __shfl_xor(m, o, 64), __shfl_xor(s, o, 64));
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) {
-    red_m[w] = m;
-    red_s[w] = s;
-  }
-  __syncthreads();
+  const float l = xr_row_lse(row, V);
   if (threadIdx.x == 0) {
-    float M = red_m[0], S = red_s[0];
-#pragma unroll
-    for (int i = 1; i < 4; ++i) lse_merge(M, S, red_m[i], red_s[i]);
-    const float l = M + logf(S);
     loss[r] = valid ? l - bf2f(row[t]) : 0.f;  // read before the block overwrites the row
     lse_out[r] = l;
-    bcast = l * XR_LOG2E;
+    bcast = l * LOG2E;
   }
   __syncthreads();
   const float l2 = bcast;
@@ -173,7 +153,7 @@ __global__ void __launch_bounds__(256) xent_rows_fwd_grad_kernel(bf16_t* __restr
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const int col = c + k;
-      float p = (valid && col < V) ? fexp2(fmaf(v[k], XR_LOG2E, -l2)) : 0.f;
+      float p = (valid && col < V) ? fexp2(fmaf(v[k], LOG2E, -l2)) : 0.f;
       if (col == t) p -= 1.f;
       v[k] = p;
     }
@@ -249,7 +229,7 @@ __global__ void __launch_bounds__(512) xent_rows_reg_kernel(bf16_t* __restrict__
 #pragma unroll
   for (int j = 0; j < NCH; ++j) xr_opaque(d[j]);
   // pass 2: e = exp(l - M) (0 past V), summed in fp32, kept as bf16
-  const float m2 = M * XR_LOG2E;
+  const float m2 = M * LOG2E;
   float s = 0.f;
 #pragma unroll
   for (int j = 0; j < NCH; ++j) {
@@ -257,10 +237,10 @@ __global__ void __launch_bounds__(512) xent_rows_reg_kernel(bf16_t* __restrict__
     xr_unpack8(d[j], v);
     if ((full && j < NCH - 1) || j * 4096 + 8 <= remV) {
 #pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] = fexp2(fmaf(v[k], XR_LOG2E, -m2));
+      for (int k = 0; k < 8; ++k) v[k] = fexp2(fmaf(v[k], LOG2E, -m2));
     } else {
 #pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] = j * 4096 + k < remV ? fexp2(fmaf(v[k], XR_LOG2E, -m2)) : 0.f;
+      for (int k = 0; k < 8; ++k) v[k] = j * 4096 + k < remV ? fexp2(fmaf(v[k], LOG2E, -m2)) : 0.f;
     }
 #pragma unroll
     for (int k = 0; k < 8; ++k) s += v[k];
@@ -290,7 +270,7 @@ __global__ void __launch_bounds__(512) xent_rows_reg_kernel(bf16_t* __restrict__
     }
   }
   if (owner) {  // same thread, same address, after its vector store of this piece
-    row[tt] = f2bf(fexp2(fmaf(vt, XR_LOG2E, -l * XR_LOG2E)) - 1.f);
+    row[tt] = f2bf(fexp2(fmaf(vt, LOG2E, -l * LOG2E)) - 1.f);
     loss[blockIdx.x] = l - vt;
   }
   if (tid == 0) {
@@ -299,14 +279,12 @@ __global__ void __launch_bounds__(512) xent_rows_reg_kernel(bf16_t* __restrict__
   }
 }
 
-static int xent_rows_reg_mode() { return 1; }
-
 bool launch_xent_rows_fwd_grad(uint16_t* lg, int64_t ld, int V, const int64_t* tgt, int64_t R, float* loss,
                                float* lse, hipStream_t s) {
   if (ld % 8 != 0 || V > ld || V <= 0) return false;
   if (R <= 0) return true;
   const int nch = (int)((ld + 4095) / 4096);
-  if (xent_rows_reg_mode() && nch <= 16) {
+  if (nch <= 16) {
     // instantiated widths; a row between two of them takes the wider one (extra pieces masked)
     const int up = nch <= 4 ? nch : nch <= 6 ? 6 : nch <= 8 ? 8 : nch <= 10 ? 10 : nch <= 13 ? 13 : 16;
 #define DPA_XROWS_REG(N)                                                                            \

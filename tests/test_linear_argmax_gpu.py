@@ -25,9 +25,10 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 # (N, V, E): partial token block + partial last W tile | E = 256, V no multiple of 64 | the real
 # vocabulary, many splits on a 2-D grid | 8 splits, the one-split-per-XCD 1-D grid | one token
-# block past the no-split threshold (1024 blocks): a single sweep of the vocabulary | one token
+# block past the no-split threshold (1024 blocks): a single sweep of the vocabulary | one token |
+# E = 256 on the one-split-per-XCD 1-D grid, partial last token block
 SHAPES = [(300, 1000, 128), (130, 517, 256), (4096, 30522, 128), (16384, 1000, 128), (131000, 500, 128),
-          (1, 1000, 128)]
+          (1, 1000, 128), (16400, 1000, 256)]
 _CACHE = {}
 
 

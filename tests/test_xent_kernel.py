@@ -17,10 +17,11 @@ def _ref(x, W, b, tgt):
 
 
 # N < 98304: lxent_fwd_dx splits the vocabulary over blocks and merges (m, l, u) partials;
-# 131072 tokens: one block per 128 tokens sweeps the whole vocabulary
+# 131072 tokens: one block per 128 tokens sweeps the whole vocabulary;
+# (16400, 1000, 256): lxent_fwd's E = 256 kernel on the one-split-per-XCD 1-D grid (8 splits)
 @pytest.mark.parametrize("N,V,E,with_bias", [(300, 1000, 128, True), (4096, 30522, 128, True),
                                                (130, 517, 256, False), (70000, 2000, 128, True),
-                                               (131072, 1000, 128, True)])
+                                               (131072, 1000, 128, True), (16400, 1000, 256, False)])
 def test_lxent_fwd_bwd(N, V, E, with_bias):
     torch.manual_seed(0)
     dev = "cuda"
