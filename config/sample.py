@@ -32,6 +32,23 @@ class DecodeSettings(S):
     clamp_step: int \
         = _(-1, "Round the predicted x0 to its nearest word embedding at the reverse steps t <= clamp_step; "
                 "-1 = at every step.")
+    step: int \
+        = _(0, "Reverse steps of the respaced chain (2 .. diffusion_steps); 0 = all diffusion_steps.")
+    sampler: Choice("ancestral", "ddim") \
+        = _("ancestral", "Reverse update: ancestral (DDPM posterior) or ddim.")
+    ddim_eta: float \
+        = _(0.0, "DDIM eta (0 = deterministic updates, 1 = the ancestral posterior variance).")
+    top_p: float \
+        = _(0.0, "Truncate every step's noise to [-top_p, top_p] (DiffuSeq --top_p); 0 = off.")
+    mbr: int \
+        = _(1, "Candidates decoded per source; recover is their minimum-Bayes-risk pick (utils/mbr.py).")
+    noise: Choice("torch", "philox") \
+        = _("torch", "torch: one torch.Generator seeded with seed (the output depends on the batching). "
+                     "philox: counter-based noise keyed by (seed + candidate, step, sample index in the split, "
+                     "position), so the output does not depend on the batching; on a GPU the reverse update "
+                     "is then one fused kernel per step.")
+    keep_candidates: bool \
+        = _(False, "Also write every candidate's ids as `candidates` to each output row.")
     seed: int \
         = _(102, "Sampling seed.")
     out_path: str \

@@ -195,6 +195,17 @@ bool launch_diff_loss_bwd(const float* x_start, const void* out, bool out_bf16, 
 void launch_timestep_emb(const float* ts, int B, int dim, float max_period, uint16_t* out,
                          hipStream_t s);
 
+// ---- reverse_step.hip: one DiffuSeq reverse-process update (decoding) ------------------
+// out[n] = mask[n] == 0 ? x_start[n] : a x0[n] + b x[n] + s z[n], x0 = pred (bf16) or scale * W[idx[n]]
+// (ids outside [0, V): a zero row); z from Philox keyed by (seed, step) and counted by the global
+// group index ((row_base + n) E + c) / 4, truncated to [-tau, tau] when tau > 0 (erf_tau =
+// erf(tau / sqrt 2)).  x may be null when b == 0, pred / idx / W when a == 0, mask / x_start and
+// out16 (the bf16 copy) always.  false: E % 4 != 0, N <= 0 or a required pointer is null.
+bool launch_reverse_step(const float* x, const uint16_t* pred, const int64_t* idx, const float* W,
+                         const float* x_start, const int64_t* mask, int64_t N, int E, int V, float scale,
+                         float a, float b, float s, uint64_t seed, uint32_t step, uint64_t row_base,
+                         float tau, float erf_tau, float* out, uint16_t* out16, hipStream_t st);
+
 // ---- sort.hip: counting sort of token ids, stable 0/1 partition ---------------------
 // STABLE counting sort of ids into V + 1 buckets (out-of-range ids -> bucket V); ws:
 // id_sort_workspace_ints(n, V) ints.  Equal ids end up adjacent in index order (the same

@@ -168,12 +168,94 @@ class GaussianDiffusion:
             x, _ = self.p_sample(model, x, t, mask, x_start, clip_denoised, fn, generator=generator)
         return x
 
+    # -- respaced / DDIM sampling ---------------------------------------------
+    def kept_timesteps(self, steps):
+        """The ``steps`` original timesteps a respaced chain keeps: evenly spread over
+        [0, T - 1] with both ends kept, strictly increasing; ``steps == T`` keeps all."""
+        T, S = self.num_timesteps, int(steps)
+        if not 2 <= S <= T:
+            raise ValueError(f"steps must lie in [2, {T}], got {steps}")
+        return [(2 * i * (T - 1) + (S - 1)) // (2 * (S - 1)) for i in range(S)]
+
+    def reverse_schedule(self, steps=None, sampler="ancestral", eta=0.0):
+        """-> [(t_model, a, b, s)] from the last kept step down to the first: the update of
+        every sampler on the target positions is ``x_prev = a x0_hat + b x_t + s z`` and the
+        model is always asked at the original timestep ``t_model``.  Computed in float64 from
+        ``alphas_cumprod`` over the kept timesteps k_i (``steps=None``: all T):
+
+            ab_i = alphas_cumprod[k_i], ab_{-1} = 1, beta'_i = 1 - ab_i / ab_{i-1}
+            ancestral: a = beta' sqrt(ab_{i-1}) / (1 - ab_i),
+                       b = (1 - ab_{i-1}) sqrt(1 - beta') / (1 - ab_i),
+                       s^2 = beta' (1 - ab_{i-1}) / (1 - ab_i) if sigma_small else beta'
+            ddim(eta): sigma = eta sqrt((1 - ab_{i-1}) / (1 - ab_i)) sqrt(1 - ab_i / ab_{i-1}),
+                       b = sqrt(max(1 - ab_{i-1} - sigma^2, 0)) / sqrt(1 - ab_i),
+                       a = sqrt(ab_{i-1}) - b sqrt(ab_i), s = sigma
+            s = 0 at i = 0 (the last update adds no noise)."""
+        if sampler not in ("ancestral", "ddim"):
+            raise ValueError(f"unknown sampler {sampler!r} (ancestral or ddim)")
+        kept = self.kept_timesteps(self.num_timesteps if steps is None else steps)
+        ab = self.alphas_cumprod[kept]
+        ab_prev = np.append(1.0, ab[:-1])
+        beta = 1.0 - ab / ab_prev
+        if sampler == "ancestral":
+            a = beta * np.sqrt(ab_prev) / (1.0 - ab)
+            b = (1.0 - ab_prev) * np.sqrt(1.0 - beta) / (1.0 - ab)
+            var = beta * (1.0 - ab_prev) / (1.0 - ab) if self.model_var_type == "fixed_small" else beta
+            s = np.sqrt(var)
+        else:
+            s = float(eta) * np.sqrt((1.0 - ab_prev) / (1.0 - ab)) * np.sqrt(beta)
+            b = np.sqrt(np.maximum(1.0 - ab_prev - s * s, 0.0)) / np.sqrt(1.0 - ab)
+            a = np.sqrt(ab_prev) - b * np.sqrt(ab)
+        s[0] = 0.0
+        return [(int(kept[i]), float(a[i]), float(b[i]), float(s[i])) for i in reversed(range(len(kept)))]
+
     @torch.no_grad()
-    def sample_seq2seq(self, model, batch, *, clamp_step=None, generator=None):
+    def _reverse_loop(self, model, net, x_start, mask, sched, clamp_step, c, *, generator, noise_seed,
+                      row_base, top_p):
+        """The reverse loop over ``sched`` through ``ops.diffusion.reverse_step``.  With an integer
+        ``noise_seed`` the noise is the op's own (on a GPU: drawn inside the fused kernel, keyed
+        by (noise_seed, position in the chain, row_base + row)), a rounded prediction reaches the
+        op as token ids + the embedding table, the model reads the op's bf16 output, and nothing
+        in the loop synchronises with the host.  Otherwise the noise comes from ``generator``."""
+        from ..ops import diffusion as dops
+        seeded = noise_seed is not None
+        dev, B, S = x_start.device, x_start.shape[0], len(sched)
+        W, scale = net.word_embedding.weight.detach(), net.emb_scale_factor
+        want16 = seeded and getattr(net, "compute_dtype", None) == torch.bfloat16
+        kw = dict(x_start=x_start, mask=mask, seed=noise_seed if seeded else 0, row_base=row_base)
+
+        def noise(top_p):
+            return None if seeded else dops.draw_noise(x_start.shape, dev, generator, top_p)
+
+        # step ids: S for the start noise (never truncated: DiffuSeq's top_p acts on the steps'
+        # noise only), then the chain position S - 1 .. 0
+        x, x16 = dops.reverse_step(None, a=0.0, b=0.0, s=1.0, step=S, noise=noise(0.0), want_bf16=want16, **kw)
+        for j, (k, a, b, s) in enumerate(sched):
+            t = torch.full((B,), k, dtype=torch.long, device=dev)
+            pred = model(x if x16 is None else x16, self.scale_timesteps(t))
+            if not seeded:
+                pred = pred.float()
+            src = dict(pred=pred)
+            if clamp_step is None or k <= clamp_step:
+                src = dict(idx=net.nearest_tokens(pred, c), weight=W, scale=scale)
+            x, x16 = dops.reverse_step(x, a=a, b=b, s=s, step=S - 1 - j, top_p=top_p,
+                                       noise=noise(top_p) if s != 0.0 else None, want_bf16=want16, **src, **kw)
+        return x
+
+    @torch.no_grad()
+    def sample_seq2seq(self, model, batch, *, clamp_step=None, generator=None, steps=None,
+                       sampler="ancestral", eta=0.0, top_p=0.0, noise_seed=None, row_base=0):
         """Decode the target half of ``batch`` (``input_ids`` [B, L]; ``input_mask`` 1 on the
         target positions) with the reverse process, the source positions kept at their word
-        embeddings; every predicted x_0 (at the steps t <= clamp_step; None: all) is rounded to
-        its nearest word embedding.
+        embeddings; every predicted x_0 (at the steps t <= clamp_step, an original timestep;
+        None: all) is rounded to its nearest word embedding.
+
+        steps / sampler / eta: the chain of :meth:`reverse_schedule` (None: all T steps).
+        top_p = tau > 0: every step's noise is truncated to [-tau, tau].  noise_seed (int): the
+        noise is keyed by (noise_seed, step, row_base + sample row, column) instead of coming from
+        ``generator``, so a sample decodes to the same result in whatever batch it is placed
+        (``row_base``: the index of the batch's first sample in the data); on a GPU the whole
+        update outside the model is then one kernel per step (``ops.diffusion.reverse_step``).
 
         -> {"tokens": [B, L] ids, the source positions copied from ``input_ids``;
             "x0": [B, L, E] fp32, the final sample; "source_mask": [B, L] bool}"""
@@ -185,8 +267,15 @@ class GaussianDiffusion:
         def round_fn(x, t):
             return net.round_to_embeds(x, c)
 
-        x0 = self.p_sample_loop(model, x_start.shape, mask=input_mask, x_start=x_start, denoised_fn=round_fn,
-                                device=x_start.device, clamp_step=clamp_step, generator=generator)
+        if noise_seed is None and steps is None and sampler == "ancestral" and top_p <= 0:
+            x0 = self.p_sample_loop(model, x_start.shape, mask=input_mask, x_start=x_start, denoised_fn=round_fn,
+                                    device=x_start.device, clamp_step=clamp_step, generator=generator)
+        else:
+            sched = self.reverse_schedule(steps, sampler, eta)
+            L = input_ids.shape[1]
+            x0 = self._reverse_loop(model, net, x_start.contiguous(), input_mask, sched, clamp_step, c,
+                                    generator=generator, noise_seed=noise_seed, row_base=int(row_base) * L,
+                                    top_p=float(top_p))
         source = input_mask == 0
         tokens = torch.where(source, input_ids, net.decode_tokens(x0))
         return {"tokens": tokens, "x0": x0, "source_mask": source}

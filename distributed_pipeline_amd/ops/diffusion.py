@@ -11,11 +11,17 @@ Fused DiffuSeq diffusion-side ops on the gfx950 kernels of ``csrc/diffusion.hip`
   against the un-noised embedding) and ``tT`` terms, one workgroup per sample;
   the backward writes d(model output) in its dtype and d(x_start) in fp32.
 * :func:`timestep_embedding` - sinusoidal [cos | sin] embedding straight to bf16.
+* :func:`reverse_step` - one reverse-process update of decoding,
+  ``a x0_hat + b x_t + s z`` with the source rows kept, as one kernel
+  (``csrc/reverse_step.hip``) with batch-independent in-kernel noise; it carries
+  its own PyTorch path for the CPU / fp32.
 
-Only used for HIP tensors of a bf16 model; the PyTorch formulas in
-``models/gaussian_diffusion.py`` are the CPU / fp32 path and the numerics oracle
+The training ops are only used for HIP tensors of a bf16 model; the PyTorch formulas
+in ``models/gaussian_diffusion.py`` are the CPU / fp32 path and the numerics oracle
 of ``tests/test_diffusion_kernels.py``.
 """
+import math
+
 import torch
 
 from ._ext import get_ext
@@ -113,6 +119,105 @@ def diffusion_mse(x_start, out, ids, t, W, sqrt_alpha_bar_last, t0_via_x_start=F
     embedding gradient may be routed through d x_start (deterministic)."""
     return _DiffLossFn.apply(x_start, out.contiguous(), ids.contiguous(), t.to(torch.long).contiguous(),
                              W, float(sqrt_alpha_bar_last), bool(t0_via_x_start))
+
+
+def _erf_tau(top_p):
+    """erf(tau / sqrt 2) in double: the mass of the standard normal inside [-tau, tau]."""
+    return math.erf(float(top_p) / math.sqrt(2.0))
+
+
+def step_generator(seed, step, device):
+    """The ``torch.Generator`` of the PyTorch path's noise at (seed, step)."""
+    g = torch.Generator(device=device)
+    g.manual_seed((int(seed) * 1000003 + int(step)) % (2 ** 63))
+    return g
+
+
+def draw_noise(shape, device, generator, top_p=0.0):
+    """Standard normal noise from ``generator``; with ``top_p`` = tau > 0 truncated to [-tau, tau]
+    by inverse CDF (the distribution DiffuSeq's re-draw loop produces, without the loop)."""
+    if top_p <= 0:
+        return torch.randn(shape, dtype=torch.float32, device=device, generator=generator)
+    u = torch.rand(shape, dtype=torch.float64, device=device, generator=generator)
+    u = u.clamp_(2.0 ** -53, 1.0 - 2.0 ** -53)
+    z = math.sqrt(2.0) * torch.erfinv((2.0 * u - 1.0) * _erf_tau(top_p))
+    return z.clamp_(-float(top_p), float(top_p)).float()
+
+
+def reverse_step(x, *, pred=None, idx=None, weight=None, scale=1.0, x_start=None, mask=None, a, b, s,
+                 seed, step, row_base=0, top_p=0.0, noise=None, want_bf16=False):
+    """One DiffuSeq reverse-process update ``[..., E]`` -> ``(out fp32, out bf16 | None)``:
+
+        x0  = pred                          (the model's prediction)
+              or scale * weight[idx]        (its rounding; ids outside [0, V): a zero row)
+        y   = a * x0 + b * x + s * z
+        out = where(mask == 0, x_start, y)  (mask [...] marks the target positions)
+
+    ``x`` may be None when b == 0 and ``pred`` / ``idx`` when a == 0; a = b = 0, s = 1 draws the
+    start noise.  On a HIP device with fp32 ``x`` / ``x_start``, a bf16 ``pred`` or an fp32
+    ``weight``, E % 4 == 0 and no explicit ``noise`` this is one kernel (csrc/reverse_step.hip)
+    whose z depends on (seed, step, row_base + row, column) only - not on the batch a row is in -
+    and is truncated to [-top_p, top_p] when top_p > 0.  Anything else evaluates the same formula
+    in fp32 PyTorch with ``noise`` or, without it, noise from a generator seeded with
+    (seed, step): the same distribution, other bits, reproducible for the same batch."""
+    ref = next((t for t in (x, pred, x_start) if t is not None), None)
+    if ref is None:
+        raise ValueError("reverse_step: one of x, pred, x_start must be given (it fixes the shape)")
+    if idx is not None and pred is None and weight is None:
+        raise ValueError("reverse_step: idx needs weight")
+    if mask is not None and x_start is None:
+        raise ValueError("reverse_step: mask needs x_start")
+    a, b, s = float(a), float(b), float(s)
+    if (b != 0.0 and x is None) or (a != 0.0 and pred is None and idx is None):
+        raise ValueError("reverse_step: b != 0 needs x, a != 0 needs pred or idx")
+    shape, dev = ref.shape, ref.device
+    E = int(shape[-1])
+    if _kernel_ok(dev, E, x, pred, idx, weight, x_start, noise):
+        N = ref.numel() // E
+        m = None if mask is None else mask.reshape(-1).to(torch.long).contiguous()
+        ids = None if idx is None or pred is not None else idx.reshape(-1).to(torch.long).contiguous()
+        out, out16 = get_ext().reverse_step(
+            ref, N, E, x=_c(x), pred=_c(pred), idx=ids, W=None if ids is None else weight.detach().contiguous(),
+            x_start=_c(x_start), mask=m, scale=float(scale),
+            a=a, b=b, s=s, seed=int(seed), step=int(step), row_base=int(row_base), tau=max(float(top_p), 0.0),
+            erf_tau=_erf_tau(top_p) if top_p > 0 else 0.0, want_bf16=bool(want_bf16))
+        return out.view(shape), (out16.view(shape) if want_bf16 else None)
+    y = torch.zeros(shape, dtype=torch.float32, device=dev)
+    if a != 0.0:
+        if pred is not None:
+            x0 = pred.float()
+        else:
+            V = weight.shape[0]
+            ok = (idx >= 0) & (idx < V)
+            x0 = float(scale) * weight.detach().float()[idx.clamp(0, V - 1)] * ok.unsqueeze(-1)
+        y = y + a * x0
+    if b != 0.0:
+        y = y + b * x.float()
+    if s != 0.0:
+        if noise is None:
+            noise = draw_noise(shape, dev, step_generator(seed, step, dev), top_p)
+        y = y + s * noise.float()
+    if mask is not None:
+        y = torch.where(mask.unsqueeze(-1) == 0, x_start.float(), y)
+    return y, (y.to(torch.bfloat16) if want_bf16 else None)
+
+
+def _kernel_ok(dev, E, x, pred, idx, weight, x_start, noise):
+    if dev.type != "cuda" or noise is not None or E % 4 != 0:
+        return False
+    if any(t is not None and t.dtype != torch.float32 for t in (x, x_start)):
+        return False
+    if pred is not None:
+        if pred.dtype != torch.bfloat16:
+            return False
+    elif idx is not None and weight.dtype != torch.float32:
+        return False
+    ext = get_ext()
+    if ext is None:
+        return False
+    if not hasattr(ext, "reverse_step"):
+        raise RuntimeError("the native extension has no reverse_step kernel: rebuild it")
+    return True
 
 
 def timestep_embedding(timesteps, dim, max_period=10000):

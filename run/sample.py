@@ -9,8 +9,16 @@ with every predicted x0 rounded to its nearest word embedding
 a ``vocab.txt``.
 
 ``--config_json`` takes the ``training_args.json`` of the training run as it is
-(config/sample.py).  A seed reproduces the output: the sampling noise comes from one generator
-seeded with ``seed``.
+(config/sample.py).  A seed reproduces the output: by default the sampling noise comes from one
+generator seeded with ``seed``.
+
+``--step S`` decodes with a respaced chain of S steps, ``--sampler ddim --ddim_eta`` with DDIM
+updates, ``--top_p`` truncates every step's noise, and ``--mbr K`` decodes K candidates per source
+and writes their minimum-Bayes-risk pick (``--keep_candidates true``: all of them too).  With
+``--noise philox`` the noise is keyed by (seed + candidate, step, index of the sample in the split,
+position) instead: the output no longer depends on ``batch_size``, ``--mbr K --seed s`` gives the
+candidates that K runs with ``--mbr 1`` and the seeds s .. s + K - 1 give, and on a GPU each
+reverse update outside the model is one fused kernel.
 """
 import json
 import os
@@ -94,6 +102,7 @@ def main(namespace):
     from data import load_data_from_args
     from data.dataset import PAD_ID
     from utils.initialization import create_diffusion_from_config, create_model_from_config
+    from utils.mbr import mbr_select
 
     if args.model != "diffuseq":
         raise ValueError(f"run.sample decodes the diffuseq model, not {args.model!r}")
@@ -125,22 +134,37 @@ def main(namespace):
     gen = torch.Generator(device=dev)
     gen.manual_seed(args.seed)
     clamp_step = None if args.clamp_step < 0 else args.clamp_step
+    if args.mbr < 1:
+        raise ValueError(f"--mbr must be >= 1, got {args.mbr}")
+    chain = dict(steps=args.step or None, sampler=args.sampler, eta=args.ddim_eta, top_p=args.top_p)
     n = 0
     with open(out_path, "w") as fout:
         for b, batch in enumerate(data):
             if b >= args.num_batches:
                 break
             batch = {k: v.to(dev) for k, v in batch.items()}
-            out = diffusion.sample_seq2seq(model, batch, clamp_step=clamp_step, generator=gen)
-            ids, mask, rec = batch["input_ids"].cpu(), batch["input_mask"].cpu(), out["tokens"].cpu()
+            recs = []
+            for c in range(args.mbr):
+                if args.noise == "philox":  # candidate c is what seed + c alone decodes; n: first sample's index
+                    out = diffusion.sample_seq2seq(model, batch, clamp_step=clamp_step, noise_seed=args.seed + c,
+                                                   row_base=n, **chain)
+                else:
+                    out = diffusion.sample_seq2seq(model, batch, clamp_step=clamp_step, generator=gen, **chain)
+                recs.append(out["tokens"].cpu())
+            ids, mask = batch["input_ids"].cpu(), batch["input_mask"].cpu()
             for i in range(ids.shape[0]):
-                src, ref, hyp = split_sample(ids[i], mask[i], rec[i], PAD_ID)
+                cands = [split_sample(ids[i], mask[i], rec[i], PAD_ID) for rec in recs]
+                src, ref = cands[0][:2]
+                hyps = [cand[2] for cand in cands]
+                hyp = hyps[mbr_select(hyps)]
                 line = {"source": src, "reference": ref, "recover": hyp}
+                if args.keep_candidates:
+                    line["candidates"] = hyps
                 if vocab is not None:
                     line.update(source_text=detokenize(src, vocab), reference_text=detokenize(ref, vocab),
                                 recover_text=detokenize(hyp, vocab))
                 fout.write(json.dumps(line) + "\n")
-                n += 1
+            n += ids.shape[0]
     print(f"### wrote {n} samples to {out_path}")
     return out_path
 
