@@ -1,0 +1,18 @@
+"""
+Evaluation settings (L4) for ``python -m run.eval``.
+"""
+from typing import final
+
+from .base import S, Item as _
+
+
+@final
+class EvalSettings(S):
+    path: str \
+        = _(..., "A .jsonl file written by run.sample: rows with `recover` and `reference` token ids and, "
+                 "from --keep_candidates true, `candidates`.")
+    batch_size: int \
+        = _(4096, "Rows scored per n-gram match call.")
+
+
+__all__ = ('EvalSettings',)

@@ -1126,6 +1126,28 @@ static std::vector<at::Tensor> reverse_step(const at::Tensor& like, int64_t N, i
   return {out, out16};
 }
 
+// Clipped n-gram match counts of every pair of a group's K sequences (csrc/ngram_match.hip):
+// tokens [G, K, L] int32 / int64, lens [G, K] int32 -> int32 [G, K, K, 4], or None for a shape the
+// kernel does not cover.
+static c10::optional<at::Tensor> ngram_matches(const at::Tensor& tokens, const at::Tensor& lens) {
+  CHECK_DEV(tokens); CHECK_CONTIG(tokens); CHECK_DEV(lens); CHECK_CONTIG(lens);
+  TORCH_CHECK(tokens.scalar_type() == at::kInt || tokens.scalar_type() == at::kLong,
+              "ngram_matches: tokens must be int32 or int64");
+  TORCH_CHECK(lens.scalar_type() == at::kInt, "ngram_matches: lens must be int32");
+  TORCH_CHECK(tokens.dim() == 3 && lens.dim() == 2 && lens.size(0) == tokens.size(0) &&
+                  lens.size(1) == tokens.size(1) && lens.device() == tokens.device(),
+              "ngram_matches: tokens [G, K, L], lens [G, K] on one device");
+  const int64_t G = tokens.size(0), K = tokens.size(1), L = tokens.size(2);
+  const c10::DeviceGuard guard(tokens.device());
+  at::Tensor m = at::empty({G, K, K, 4}, tokens.options().dtype(at::kInt));
+  if (G == 0) return m;
+  if (K > 0x7fffffffLL || L > 0x7fffffffLL) return c10::nullopt;
+  if (!dpa::launch_ngram_match(tokens.data_ptr(), tokens.scalar_type() == at::kLong, lens.data_ptr<int>(), G,
+                               (int)K, (int)L, m.data_ptr<int>(), cur_stream()))
+    return c10::nullopt;
+  return m;
+}
+
 static void emb_qsample_bwd(const at::Tensor& ids, const at::Tensor& mask, const at::Tensor& t,
                             const at::Tensor& sa, c10::optional<at::Tensor> d_xs,
                             c10::optional<at::Tensor> d_xs16, c10::optional<at::Tensor> d_xt,
@@ -1367,6 +1389,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("mask") = py::none(), py::arg("scale") = 1.0, py::arg("a") = 0.0, py::arg("b") = 0.0,
         py::arg("s") = 0.0, py::arg("seed") = 0, py::arg("step") = 0, py::arg("row_base") = 0,
         py::arg("tau") = 0.0, py::arg("erf_tau") = 0.0, py::arg("want_bf16") = false);
+  m.def("ngram_matches", &ngram_matches,
+        "clipped 1..4-gram match counts of every sequence pair of a group -> int32 [G, K, K, 4] | None (shape not covered)",
+        py::arg("tokens"), py::arg("lens"));
   m.def("emb_qsample_bwd", &emb_qsample_bwd, "scatter-add of the q_sample gradients into dW (fp32)");
   m.def("diff_loss_fwd", &diff_loss_fwd, "DiffuSeq per-sample (mse, tT) losses");
   m.def("diff_loss_bwd", &diff_loss_bwd, "backward of diff_loss_fwd -> (d_out, d_x_start)", py::arg("xs"),

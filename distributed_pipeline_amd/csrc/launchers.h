@@ -206,6 +206,14 @@ bool launch_reverse_step(const float* x, const uint16_t* pred, const int64_t* id
                          float a, float b, float s, uint64_t seed, uint32_t step, uint64_t row_base,
                          float tau, float erf_tau, float* out, uint16_t* out16, hipStream_t st);
 
+// ---- ngram_match.hip: clipped n-gram match counts of sequence pairs (MBR, BLEU) --------
+// m[g][i][j][n-1] = sum over the distinct n-grams y of min(count_i(y), count_j(y)), n = 1..4, for the
+// K sequences tokens[g][k][0 .. lens[g][k]) of every group (ids there in [0, 2^31); lens clamped to
+// [0, L]; int32 or int64 ids).  Exact integers, no atomics.  false: a shape outside 1 <= K <= 16,
+// 1 <= L <= 256, 1 <= G < 2^31, or a null pointer.
+bool launch_ngram_match(const void* tokens, bool tok64, const int* lens, int64_t G, int K, int L, int* m,
+                        hipStream_t st);
+
 // ---- sort.hip: counting sort of token ids, stable 0/1 partition ---------------------
 // STABLE counting sort of ids into V + 1 buckets (out-of-range ids -> bucket V); ws:
 // id_sort_workspace_ints(n, V) ints.  Equal ids end up adjacent in index order (the same

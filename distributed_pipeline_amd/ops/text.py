@@ -1,0 +1,73 @@
+"""
+Token-sequence ops of decoding and evaluation on the gfx950 kernel of ``csrc/ngram_match.hip``.
+
+* :func:`ngram_matches` - the clipped 1..4-gram match counts between every pair of a group's
+  sequences, the quantity sentence BLEU, minimum-Bayes-risk selection and self-BLEU are built on
+  (``utils/mbr.py``).  Integers only: the kernel and the PyTorch path give the same tensor.
+"""
+import torch
+
+from ._ext import get_ext
+
+_FALLBACK_ELEMS = 1 << 25  # pairwise comparisons (bools) one chunk of groups may hold
+
+
+def ngram_matches(tokens, lens):
+    """``tokens`` [G, K, L] (int32 / int64, any strides), ``lens`` [G, K] -> int32 [G, K, K, 4]:
+
+        m[g, i, j, n - 1] = sum over the distinct n-grams y of min(count_i(y), count_j(y)),  n = 1..4
+
+    where count_k counts the occurrences of y among the first ``lens[g, k]`` (clamped to [0, L], on
+    the device) tokens of sequence k.  Positions at or beyond the length never count, whatever
+    they hold; the ids inside the lengths must lie in [0, 2^31).  m is symmetric in (i, j) and its
+    diagonal is max(len - n + 1, 0).
+
+    On a HIP device with the extension and a shape the kernel covers (K <= 16, L <= 256) this is one
+    kernel; anything else evaluates the same definition in PyTorch, chunked over G."""
+    if tokens.dim() != 3 or lens.shape != tokens.shape[:2]:
+        raise ValueError(f"ngram_matches: tokens [G, K, L] and lens [G, K], got {tuple(tokens.shape)} "
+                         f"and {tuple(lens.shape)}")
+    if tokens.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"ngram_matches: tokens must be int32 or int64, not {tokens.dtype}")
+    G, K, L = tokens.shape
+    lens = lens.to(tokens.device).clamp(0, L).to(torch.int32).contiguous()
+    if tokens.is_cuda:
+        ext = get_ext()
+        if ext is not None:
+            if not hasattr(ext, "ngram_matches"):
+                raise RuntimeError("the native extension has no ngram_matches kernel: rebuild it")
+            m = ext.ngram_matches(tokens.contiguous(), lens)
+            if m is not None:
+                return m
+    return _ngram_matches_torch(tokens, lens)
+
+
+def _ngram_matches_torch(tokens, lens):
+    """The definition in rank/count form: position p of sequence i is a clipped match against j
+    when its n-gram occurs more often in j than it has occurred in i before p."""
+    G, K, L = tokens.shape
+    out = torch.zeros((G, K, K, 4), dtype=torch.int32, device=tokens.device)
+    if G == 0 or K == 0 or L == 0:
+        return out
+    chunk = max(1, _FALLBACK_ELEMS // (K * K * L * L))
+    pos = torch.arange(L, device=tokens.device)
+    below = (pos.view(1, L) < pos.view(L, 1)).view(1, 1, L, L)  # [.., p, q]: q < p
+    for g0 in range(0, G, chunk):
+        tok, ln = tokens[g0:g0 + chunk], lens[g0:g0 + chunk]
+        valid = pos.view(1, 1, L) < ln.unsqueeze(-1)                                  # [g, K, L]
+        # eq[g, i, p, j, q]: the n-grams at p of i and q of j exist and are equal (n = 1 first)
+        one = (tok.view(-1, K, L, 1, 1) == tok.view(-1, 1, 1, K, L)) \
+            & valid.view(-1, K, L, 1, 1) & valid.view(-1, 1, 1, K, L)
+        eq = one
+        for n in range(1, 5):
+            if n > 1:
+                nxt = torch.zeros_like(one)
+                s = n - 1
+                if s < L:
+                    nxt[:, :, :L - s, :, :L - s] = one[:, :, s:, :, s:]
+                eq = eq & nxt
+            count = eq.sum(-1, dtype=torch.int32)                                     # [g, i, p, j]
+            own = torch.diagonal(eq, dim1=1, dim2=3).permute(0, 3, 1, 2)              # [g, i, p, q]
+            rank = (own & below).sum(-1, dtype=torch.int32)                           # [g, i, p]
+            out[g0:g0 + chunk, :, :, n - 1] = (count > rank.unsqueeze(-1)).sum(2, dtype=torch.int32)
+    return out

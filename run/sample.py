@@ -14,7 +14,8 @@ generator seeded with ``seed``.
 
 ``--step S`` decodes with a respaced chain of S steps, ``--sampler ddim --ddim_eta`` with DDIM
 updates, ``--top_p`` truncates every step's noise, and ``--mbr K`` decodes K candidates per source
-and writes their minimum-Bayes-risk pick (``--keep_candidates true``: all of them too).  With
+and writes their minimum-Bayes-risk pick (``--keep_candidates true``: all of them too; the pick of
+a whole batch is one n-gram match kernel on the device, ``utils.mbr.mbr_select_batch``).  With
 ``--noise philox`` the noise is keyed by (seed + candidate, step, index of the sample in the split,
 position) instead: the output no longer depends on ``batch_size``, ``--mbr K --seed s`` gives the
 candidates that K runs with ``--mbr 1`` and the seeds s .. s + K - 1 give, and on a GPU each
@@ -93,6 +94,23 @@ def split_sample(ids, mask, recovered, pad_id=0):
     return source, reference, recover
 
 
+def recover_parts(recs, mask, pad_id=0):
+    """The ``recover`` parts of K decoded ``[B, L]`` id tensors as one padded batch, with tensor
+    ops on their device: -> (tokens [B, K, L], lens [B, K]) where ``tokens[b, k, :lens[b, k]]`` is
+    what :func:`split_sample` returns for sample b of candidate k - the ids after the source
+    (``mask`` == 0) up to the first ``pad_id``."""
+    import torch
+
+    rec = torch.stack(list(recs), 1)                                   # [B, K, L]
+    L = rec.shape[-1]
+    at = (mask == 0).sum(1).view(-1, 1, 1) + torch.arange(L, device=rec.device)  # position in rec
+    inside = at < L
+    tokens = rec.gather(2, at.clamp(max=L - 1).expand(rec.shape))
+    live = (inside & (tokens != pad_id)).to(torch.int32)
+    lens = live.cumprod(-1).sum(-1)                                    # tokens before the first pad
+    return tokens, lens
+
+
 def main(namespace):
     args: SampleSettings = SampleSettings.from_argparse(namespace)
 
@@ -102,7 +120,7 @@ def main(namespace):
     from data import load_data_from_args
     from data.dataset import PAD_ID
     from utils.initialization import create_diffusion_from_config, create_model_from_config
-    from utils.mbr import mbr_select
+    from utils.mbr import mbr_select_batch
 
     if args.model != "diffuseq":
         raise ValueError(f"run.sample decodes the diffuseq model, not {args.model!r}")
@@ -150,13 +168,17 @@ def main(namespace):
                                                    row_base=n, **chain)
                 else:
                     out = diffusion.sample_seq2seq(model, batch, clamp_step=clamp_step, generator=gen, **chain)
-                recs.append(out["tokens"].cpu())
+                recs.append(out["tokens"])
+            picks = None
+            if args.mbr > 1:  # the candidates stay on the device: one n-gram match kernel, one copy
+                picks = mbr_select_batch(*recover_parts(recs, batch["input_mask"], PAD_ID))
+            recs = [rec.cpu() for rec in recs]
             ids, mask = batch["input_ids"].cpu(), batch["input_mask"].cpu()
             for i in range(ids.shape[0]):
                 cands = [split_sample(ids[i], mask[i], rec[i], PAD_ID) for rec in recs]
                 src, ref = cands[0][:2]
                 hyps = [cand[2] for cand in cands]
-                hyp = hyps[mbr_select(hyps)]
+                hyp = hyps[picks[i] if picks is not None else 0]
                 line = {"source": src, "reference": ref, "recover": hyp}
                 if args.keep_candidates:
                     line["candidates"] = hyps
