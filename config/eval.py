@@ -13,6 +13,9 @@ class EvalSettings(S):
                  "from --keep_candidates true, `candidates`.")
     batch_size: int \
         = _(4096, "Rows scored per n-gram match call.")
+    rouge_l: bool \
+        = _(False, "Also report `rouge_l` (mean ROUGE-L of recover against reference) and, for rows with "
+                   "candidates, `self_rouge_l`.")
 
 
 __all__ = ('EvalSettings',)

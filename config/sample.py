@@ -42,6 +42,9 @@ class DecodeSettings(S):
         = _(0.0, "Truncate every step's noise to [-top_p, top_p] (DiffuSeq --top_p); 0 = off.")
     mbr: int \
         = _(1, "Candidates decoded per source; recover is their minimum-Bayes-risk pick (utils/mbr.py).")
+    mbr_metric: Choice("bleu", "rouge_l") \
+        = _("bleu", "Similarity the minimum-Bayes-risk pick sums over the other candidates: sentence BLEU "
+                    "(utils/mbr.py) or ROUGE-L (utils/rouge.py).")
     noise: Choice("torch", "philox") \
         = _("torch", "torch: one torch.Generator seeded with seed (the output depends on the batching). "
                      "philox: counter-based noise keyed by (seed + candidate, step, sample index in the split, "

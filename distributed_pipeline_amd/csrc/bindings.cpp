@@ -1148,6 +1148,27 @@ static c10::optional<at::Tensor> ngram_matches(const at::Tensor& tokens, const a
   return m;
 }
 
+// LCS length of every pair of a group's K sequences (csrc/lcs.hip): tokens [G, K, L] int32 / int64,
+// lens [G, K] int32 -> int32 [G, K, K], or None for a shape the kernel does not cover.
+static c10::optional<at::Tensor> lcs_lengths(const at::Tensor& tokens, const at::Tensor& lens) {
+  CHECK_DEV(tokens); CHECK_CONTIG(tokens); CHECK_DEV(lens); CHECK_CONTIG(lens);
+  TORCH_CHECK(tokens.scalar_type() == at::kInt || tokens.scalar_type() == at::kLong,
+              "lcs_lengths: tokens must be int32 or int64");
+  TORCH_CHECK(lens.scalar_type() == at::kInt, "lcs_lengths: lens must be int32");
+  TORCH_CHECK(tokens.dim() == 3 && lens.dim() == 2 && lens.size(0) == tokens.size(0) &&
+                  lens.size(1) == tokens.size(1) && lens.device() == tokens.device(),
+              "lcs_lengths: tokens [G, K, L], lens [G, K] on one device");
+  const int64_t G = tokens.size(0), K = tokens.size(1), L = tokens.size(2);
+  const c10::DeviceGuard guard(tokens.device());
+  at::Tensor out = at::empty({G, K, K}, tokens.options().dtype(at::kInt));
+  if (G == 0) return out;
+  if (K > 0x7fffffffLL || L > 0x7fffffffLL) return c10::nullopt;
+  if (!dpa::launch_lcs_lengths(tokens.data_ptr(), tokens.scalar_type() == at::kLong, lens.data_ptr<int>(), G,
+                               (int)K, (int)L, out.data_ptr<int>(), cur_stream()))
+    return c10::nullopt;
+  return out;
+}
+
 static void emb_qsample_bwd(const at::Tensor& ids, const at::Tensor& mask, const at::Tensor& t,
                             const at::Tensor& sa, c10::optional<at::Tensor> d_xs,
                             c10::optional<at::Tensor> d_xs16, c10::optional<at::Tensor> d_xt,
@@ -1391,6 +1412,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("tau") = 0.0, py::arg("erf_tau") = 0.0, py::arg("want_bf16") = false);
   m.def("ngram_matches", &ngram_matches,
         "clipped 1..4-gram match counts of every sequence pair of a group -> int32 [G, K, K, 4] | None (shape not covered)",
+        py::arg("tokens"), py::arg("lens"));
+  m.def("lcs_lengths", &lcs_lengths,
+        "longest-common-subsequence length of every sequence pair of a group -> int32 [G, K, K] | None (shape not covered)",
         py::arg("tokens"), py::arg("lens"));
   m.def("emb_qsample_bwd", &emb_qsample_bwd, "scatter-add of the q_sample gradients into dW (fp32)");
   m.def("diff_loss_fwd", &diff_loss_fwd, "DiffuSeq per-sample (mse, tT) losses");

@@ -214,6 +214,14 @@ bool launch_reverse_step(const float* x, const uint16_t* pred, const int64_t* id
 bool launch_ngram_match(const void* tokens, bool tok64, const int* lens, int64_t G, int K, int L, int* m,
                         hipStream_t st);
 
+// ---- lcs.hip: longest-common-subsequence lengths of sequence pairs (ROUGE-L) ------------
+// out[g][i][j] = LCS length of tokens[g][i][0 .. lens[g][i]) and tokens[g][j][0 .. lens[g][j]) (ids
+// there in [0, 2^31); lens clamped to [0, L]; int32 or int64 ids; out int32 [G, K, K]).  Exact
+// integers, no atomics.  false, with no launch: a shape outside 1 <= K <= 16, 1 <= L <= 256,
+// 1 <= G < 2^31 / 136, or a null pointer.
+bool launch_lcs_lengths(const void* tokens, bool tok64, const int* lens, int64_t G, int K, int L, int* out,
+                        hipStream_t st);
+
 // ---- sort.hip: counting sort of token ids, stable 0/1 partition ---------------------
 // STABLE counting sort of ids into V + 1 buckets (out-of-range ids -> bucket V); ws:
 // id_sort_workspace_ints(n, V) ints.  Equal ids end up adjacent in index order (the same

@@ -1,9 +1,12 @@
 """
-Token-sequence ops of decoding and evaluation on the gfx950 kernel of ``csrc/ngram_match.hip``.
+Token-sequence ops of decoding and evaluation on the gfx950 kernels of ``csrc/ngram_match.hip`` and
+``csrc/lcs.hip``.
 
 * :func:`ngram_matches` - the clipped 1..4-gram match counts between every pair of a group's
   sequences, the quantity sentence BLEU, minimum-Bayes-risk selection and self-BLEU are built on
   (``utils/mbr.py``).  Integers only: the kernel and the PyTorch path give the same tensor.
+* :func:`lcs_lengths` - the length of the longest common subsequence of every pair of a group's
+  sequences, the quantity ROUGE-L is built on (``utils/rouge.py``).  Integers only as well.
 """
 import torch
 
@@ -70,4 +73,59 @@ def _ngram_matches_torch(tokens, lens):
             own = torch.diagonal(eq, dim1=1, dim2=3).permute(0, 3, 1, 2)              # [g, i, p, q]
             rank = (own & below).sum(-1, dtype=torch.int32)                           # [g, i, p]
             out[g0:g0 + chunk, :, :, n - 1] = (count > rank.unsqueeze(-1)).sum(2, dtype=torch.int32)
+    return out
+
+
+def lcs_lengths(tokens, lens):
+    """``tokens`` [G, K, L] (int32 / int64, any strides), ``lens`` [G, K] -> int32 [G, K, K]:
+
+        out[g, i, j] = length of the longest common subsequence of the first ``lens[g, i]`` tokens of
+                       sequence i and the first ``lens[g, j]`` tokens of sequence j
+
+    with the lengths clamped to [0, L] (on the device).  Positions at or beyond the length never
+    match, whatever they hold; the ids inside the lengths must lie in [0, 2^31).  out is symmetric
+    in (i, j) and its diagonal is the lengths.
+
+    On a HIP device with the extension and a shape the kernel covers (K <= 16, L <= 256) this is one
+    kernel; anything else evaluates the same definition in PyTorch, chunked over G."""
+    if tokens.dim() != 3 or lens.shape != tokens.shape[:2]:
+        raise ValueError(f"lcs_lengths: tokens [G, K, L] and lens [G, K], got {tuple(tokens.shape)} "
+                         f"and {tuple(lens.shape)}")
+    if tokens.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"lcs_lengths: tokens must be int32 or int64, not {tokens.dtype}")
+    G, K, L = tokens.shape
+    lens = lens.to(tokens.device).clamp(0, L).to(torch.int32).contiguous()
+    if tokens.is_cuda:
+        ext = get_ext()
+        if ext is not None:
+            if not hasattr(ext, "lcs_lengths"):
+                raise RuntimeError("the native extension has no lcs_lengths kernel: rebuild it")
+            out = ext.lcs_lengths(tokens.contiguous(), lens)
+            if out is not None:
+                return out
+    return _lcs_lengths_torch(tokens, lens)
+
+
+def _lcs_lengths_torch(tokens, lens):
+    """The textbook dynamic programme, one row of it (one position p of sequence i) per step for all
+    pairs at once: with prev / cur the rows p and p + 1 over the prefixes of sequence j,
+    t[q + 1] = max(prev[q] + eq[q], prev[q + 1]) and cur = the running maximum of t."""
+    G, K, L = tokens.shape
+    out = torch.zeros((G, K, K), dtype=torch.int32, device=tokens.device)
+    if G == 0 or K == 0 or L == 0:
+        return out
+    chunk = max(1, _FALLBACK_ELEMS // (K * K * (L + 1)))
+    pos = torch.arange(L, device=tokens.device)
+    for g0 in range(0, G, chunk):
+        tok, ln = tokens[g0:g0 + chunk], lens[g0:g0 + chunk]
+        g = tok.shape[0]
+        valid = pos.view(1, 1, L) < ln.unsqueeze(-1)                                  # [g, K, L]
+        prev = torch.zeros((g, K, K, L + 1), dtype=torch.int32, device=tokens.device)  # [g, i, j, q]
+        for p in range(int(ln.max())):
+            eq = (tok[:, :, p].view(g, K, 1, 1) == tok.view(g, 1, K, L)) \
+                & valid[:, :, p].view(g, K, 1, 1) & valid.view(g, 1, K, L)
+            t = torch.zeros_like(prev)
+            t[..., 1:] = torch.maximum(prev[..., :-1] + eq.to(torch.int32), prev[..., 1:])
+            prev = torch.cummax(t, -1).values
+        out[g0:g0 + chunk] = prev[..., L]
     return out

@@ -7,10 +7,13 @@ Scores a file written by ``run.sample`` and prints one JSON line:
   length of ``recover``; ``dist1``: mean over rows of distinct unigrams / length (0 for an empty
   row);
 * ``self_bleu`` (rows written with ``--keep_candidates true``): mean over rows of the mean BLEU
-  of a row's candidates against each other (every ordered pair i != j) - lower is more diverse.
+  of a row's candidates against each other (every ordered pair i != j) - lower is more diverse;
+* with ``--rouge_l true`` also ``rouge_l``: mean ``rouge_l(recover, reference)`` (utils/rouge.py),
+  and ``self_rouge_l``: as ``self_bleu`` with ROUGE-L.
 
 The BLEU numbers come from ``ops.text.ngram_matches`` on the ``[recover, reference]`` pairs and on
-the candidate groups (one kernel per batch of rows on a GPU, the same integers on the CPU).
+the candidate groups (one kernel per batch of rows on a GPU, the same integers on the CPU), the
+ROUGE-L numbers from ``ops.text.lcs_lengths`` on the same padded batches.
 """
 import json
 
@@ -31,27 +34,44 @@ def _padded(groups, device):
     return tokens.to(device), lens.to(device)
 
 
-def evaluate(rows, device, batch_size=4096):
-    """The metrics of ``rows`` (dicts with ``recover``, ``reference`` and optionally ``candidates``)."""
+def evaluate(rows, device, batch_size=4096, rouge_l=False):
+    """The metrics of ``rows`` (dicts with ``recover``, ``reference`` and optionally ``candidates``);
+    ``rouge_l``: also ``rouge_l`` and, for rows with candidates, ``self_rouge_l``."""
     from utils.mbr import pairwise_bleu
+    from utils.rouge import pairwise_rouge_l
 
-    bleu, self_bleu = [], []
+    bleu, self_bleu, rouge, self_rouge = [], [], [], []
+
+    def off_diagonal(pw, k):  # mean over the ordered pairs i != j
+        return sum(pw[i][j] for i in range(k) for j in range(k) if i != j) / (k * (k - 1))
+
     for r0 in range(0, len(rows), batch_size):
         part = rows[r0:r0 + batch_size]
-        bleu += pairwise_bleu(*_padded([[r["recover"], r["reference"]] for r in part], device))[:, 0, 1].tolist()
+        pairs = _padded([[r["recover"], r["reference"]] for r in part], device)
+        bleu += pairwise_bleu(*pairs)[:, 0, 1].tolist()
+        if rouge_l:
+            rouge += pairwise_rouge_l(*pairs)[:, 0, 1].tolist()
         by_k = {}
         for r in part:
             if len(r.get("candidates", ())) > 1:
                 by_k.setdefault(len(r["candidates"]), []).append(r["candidates"])
         for k, groups in by_k.items():
-            for pb in pairwise_bleu(*_padded(groups, device)).tolist():
-                self_bleu.append(sum(pb[i][j] for i in range(k) for j in range(k) if i != j) / (k * (k - 1)))
+            cands = _padded(groups, device)
+            for pb in pairwise_bleu(*cands).tolist():
+                self_bleu.append(off_diagonal(pb, k))
+            if rouge_l:
+                for pr in pairwise_rouge_l(*cands).tolist():
+                    self_rouge.append(off_diagonal(pr, k))
     n = len(rows)
     mean = lambda xs: sum(xs) / len(xs) if xs else 0.0  # noqa: E731
     out = {"n": n, "bleu": mean(bleu), "len": mean([len(r["recover"]) for r in rows]),
            "dist1": mean([len(set(r["recover"])) / len(r["recover"]) if r["recover"] else 0.0 for r in rows])}
     if self_bleu:
         out["self_bleu"] = mean(self_bleu)
+    if rouge_l:
+        out["rouge_l"] = mean(rouge)
+        if self_rouge:
+            out["self_rouge_l"] = mean(self_rouge)
     return out
 
 
@@ -63,7 +83,7 @@ def main(namespace):
     with open(args.path) as f:
         rows = [json.loads(line) for line in f if line.strip()]
     dev = torch.device("cuda:0") if torch.cuda.is_available() else torch.device("cpu")
-    out = evaluate(rows, dev, args.batch_size)
+    out = evaluate(rows, dev, args.batch_size, rouge_l=args.rouge_l)
     print(json.dumps(out))
     return out
 

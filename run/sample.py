@@ -15,7 +15,8 @@ generator seeded with ``seed``.
 ``--step S`` decodes with a respaced chain of S steps, ``--sampler ddim --ddim_eta`` with DDIM
 updates, ``--top_p`` truncates every step's noise, and ``--mbr K`` decodes K candidates per source
 and writes their minimum-Bayes-risk pick (``--keep_candidates true``: all of them too; the pick of
-a whole batch is one n-gram match kernel on the device, ``utils.mbr.mbr_select_batch``).  With
+a whole batch is one n-gram match kernel on the device, ``utils.mbr.mbr_select_batch``;
+``--mbr_metric rouge_l`` picks by ROUGE-L instead of BLEU, on one LCS kernel).  With
 ``--noise philox`` the noise is keyed by (seed + candidate, step, index of the sample in the split,
 position) instead: the output no longer depends on ``batch_size``, ``--mbr K --seed s`` gives the
 candidates that K runs with ``--mbr 1`` and the seeds s .. s + K - 1 give, and on a GPU each
@@ -171,7 +172,7 @@ def main(namespace):
                 recs.append(out["tokens"])
             picks = None
             if args.mbr > 1:  # the candidates stay on the device: one n-gram match kernel, one copy
-                picks = mbr_select_batch(*recover_parts(recs, batch["input_mask"], PAD_ID))
+                picks = mbr_select_batch(*recover_parts(recs, batch["input_mask"], PAD_ID), metric=args.mbr_metric)
             recs = [rec.cpu() for rec in recs]
             ids, mask = batch["input_ids"].cpu(), batch["input_mask"].cpu()
             for i in range(ids.shape[0]):

@@ -6,7 +6,8 @@ source and keeps the one closest to all the others).
 ``pairwise_bleu`` take the candidates of many sources as one padded tensor: the clipped n-gram
 match counts of every pair come from one ``ops.text.ngram_matches`` call (a kernel on a GPU) and
 only the closed form ``bleu_from_counts`` is left to the host, in the same Python floats, so the
-batch pick equals ``mbr_select`` bit for bit.
+batch pick equals ``mbr_select`` bit for bit.  ``metric="rouge_l"`` selects by ROUGE-L instead
+(utils/rouge.py: LCS lengths from one ``ops.text.lcs_lengths`` call), with the same guarantee.
 """
 import math
 from collections import Counter
@@ -44,11 +45,25 @@ def sentence_bleu(hyp, ref):
     return bleu_from_counts(m[0], m[1], m[2], m[3], len(hyp), len(ref))
 
 
-def mbr_select(cands):
-    """Index of the candidate with the highest summed BLEU against the others (ties: lowest)."""
+METRICS = ("bleu", "rouge_l")
+
+
+def _check_metric(metric):
+    if metric not in METRICS:
+        raise ValueError(f"unknown MBR metric {metric!r}: one of {', '.join(METRICS)}")
+
+
+def mbr_select(cands, metric="bleu"):
+    """Index of the candidate with the highest summed ``metric`` (``bleu``: :func:`sentence_bleu`,
+    ``rouge_l``: ``utils.rouge.rouge_l``) against the others (ties: lowest)."""
+    _check_metric(metric)
+    if metric == "rouge_l":
+        from utils.rouge import rouge_l as pair_score
+    else:
+        pair_score = sentence_bleu
     best, best_score = 0, -1.0
     for i, hyp in enumerate(cands):
-        score = sum(sentence_bleu(hyp, ref) for j, ref in enumerate(cands) if j != i)
+        score = sum(pair_score(hyp, ref) for j, ref in enumerate(cands) if j != i)
         if score > best_score:
             best, best_score = i, score
     return best
@@ -75,12 +90,25 @@ def pairwise_bleu(tokens, lens):
                         dtype=torch.float64).reshape(tokens.shape[0], tokens.shape[1], tokens.shape[1])
 
 
-def mbr_select_batch(tokens, lens):
+def mbr_select_batch(tokens, lens, metric="bleu"):
     """:func:`mbr_select` of every group of ``tokens`` [G, K, L] (candidate k of group g: its first
     ``lens[g, k]`` ids) -> list of G indices, equal to the Python picks, ties included: the same
-    BLEU floats summed over j in the same order, first maximum wins."""
-    m, ln = _counts_on_host(tokens, lens)
+    BLEU (``metric="rouge_l"``: ROUGE-L, from one ``ops.text.lcs_lengths`` call) floats summed over
+    j in the same order, first maximum wins."""
+    _check_metric(metric)
     picks = []
+    if metric == "rouge_l":
+        from utils.rouge import _lcs_on_host, rouge_l_from_lcs
+
+        for cg, lg in zip(*_lcs_on_host(tokens, lens)):
+            best, best_score = 0, -1.0
+            for i, li in enumerate(lg):
+                score = sum(rouge_l_from_lcs(cg[i][j], li, lj) for j, lj in enumerate(lg) if j != i)
+                if score > best_score:
+                    best, best_score = i, score
+            picks.append(best)
+        return picks
+    m, ln = _counts_on_host(tokens, lens)
     for mg, lg in zip(m, ln):
         best, best_score = 0, -1.0
         for i, li in enumerate(lg):
