@@ -34,10 +34,13 @@ class DecodeSettings(S):
                 "-1 = at every step.")
     step: int \
         = _(0, "Reverse steps of the respaced chain (2 .. diffusion_steps); 0 = all diffusion_steps.")
-    sampler: Choice("ancestral", "ddim") \
-        = _("ancestral", "Reverse update: ancestral (DDPM posterior) or ddim.")
+    sampler: Choice("ancestral", "ddim", "dpmpp_2m", "dpmpp_2m_sde") \
+        = _("ancestral", "Reverse update: ancestral (DDPM posterior), ddim, or the second-order multistep "
+                         "DPM-Solver++ (dpmpp_2m: deterministic; dpmpp_2m_sde: with noise), which reuses the "
+                         "previous step's prediction.")
     ddim_eta: float \
-        = _(0.0, "DDIM eta (0 = deterministic updates, 1 = the ancestral posterior variance).")
+        = _(0.0, "DDIM eta (0 = deterministic updates, 1 = the ancestral posterior variance); must be 0 with "
+                 "the dpmpp samplers.")
     top_p: float \
         = _(0.0, "Truncate every step's noise to [-top_p, top_p] (DiffuSeq --top_p); 0 = off.")
     mbr: int \

@@ -1063,18 +1063,20 @@ static std::vector<at::Tensor> emb_qsample_fwd(const at::Tensor& ids, const at::
 }
 
 // One reverse-process update (csrc/reverse_step.hip).  `like` fixes the device; every given
-// tensor must hold exactly N rows (of E columns) on it.
+// tensor must hold exactly N rows (of E columns) on it.  pred_prev / idx_prev are looked at only
+// when a_prev != 0.
 static std::vector<at::Tensor> reverse_step(const at::Tensor& like, int64_t N, int64_t E,
                                             c10::optional<at::Tensor> x, c10::optional<at::Tensor> pred,
                                             c10::optional<at::Tensor> idx, c10::optional<at::Tensor> W,
                                             c10::optional<at::Tensor> x_start, c10::optional<at::Tensor> mask,
                                             double scale, double a, double b, double s, int64_t seed,
                                             int64_t step, int64_t row_base, double tau, double erf_tau,
-                                            bool want_bf16) {
+                                            bool want_bf16, c10::optional<at::Tensor> pred_prev,
+                                            c10::optional<at::Tensor> idx_prev, double a_prev) {
   CHECK_DEV(like);
   TORCH_CHECK(N >= 0 && E > 0 && E % 4 == 0 && E <= 65536, "reverse_step: N >= 0, E % 4 == 0, E <= 65536");
   TORCH_CHECK(step >= 0 && step <= 0xffffffffLL && row_base >= 0, "reverse_step: step in [0, 2^32), row_base >= 0");
-  const float af = (float)a, bf = (float)b, sf = (float)s;
+  const float af = (float)a, bf = (float)b, sf = (float)s, apf = (float)a_prev;
   auto has = [](const c10::optional<at::Tensor>& t) { return t.has_value() && t->defined(); };
   auto rows_f32 = [&](const at::Tensor& t, const char* name) -> const float* {
     TORCH_CHECK(t.is_cuda() && t.device() == like.device() && t.scalar_type() == at::kFloat && t.is_contiguous() &&
@@ -1090,19 +1092,31 @@ static std::vector<at::Tensor> reverse_step(const at::Tensor& like, int64_t N, i
   const float* xp = has(x) ? rows_f32(*x, "x") : nullptr;
   const float* xsp = has(x_start) ? rows_f32(*x_start, "x_start") : nullptr;
   const int64_t* mp = has(mask) ? rows_i64(*mask, "mask") : nullptr;
-  const uint16_t* pp = nullptr;
-  const int64_t* ip = nullptr;
+  auto rows_bf16 = [&](const at::Tensor& t, const char* name) -> const uint16_t* {
+    TORCH_CHECK(t.is_cuda() && t.device() == like.device() && t.scalar_type() == at::kBFloat16 && t.is_contiguous() &&
+                    t.numel() == N * E && reinterpret_cast<uintptr_t>(t.data_ptr()) % 8 == 0,
+                name, " must be a contiguous, 8-byte aligned bf16 [N, E] tensor on the op's device");
+    return reinterpret_cast<const uint16_t*>(t.data_ptr());
+  };
+  const uint16_t *pp = nullptr, *ppp = nullptr;
+  const int64_t *ip = nullptr, *ipp = nullptr;
   const float* wp = nullptr;
   int64_t V = 0;
   if (has(pred)) {
-    TORCH_CHECK(pred->is_cuda() && pred->device() == like.device() && pred->scalar_type() == at::kBFloat16 &&
-                    pred->is_contiguous() && pred->numel() == N * E &&
-                    reinterpret_cast<uintptr_t>(pred->data_ptr()) % 8 == 0,
-                "pred must be a contiguous, 8-byte aligned bf16 [N, E] tensor on the op's device");
-    pp = reinterpret_cast<const uint16_t*>(pred->data_ptr());
+    pp = rows_bf16(*pred, "pred");
   } else if (has(idx)) {
     TORCH_CHECK(has(W), "reverse_step: idx needs the embedding table W");
     ip = rows_i64(*idx, "idx");
+  }
+  if (apf != 0.f) {
+    if (has(pred_prev)) {
+      ppp = rows_bf16(*pred_prev, "pred_prev");
+    } else if (has(idx_prev)) {
+      TORCH_CHECK(has(W), "reverse_step: idx_prev needs the embedding table W");
+      ipp = rows_i64(*idx_prev, "idx_prev");
+    }
+  }
+  if (ip || ipp) {
     CHECK_DEV((*W)); CHECK_F32((*W)); CHECK_CONTIG((*W)); CHECK_ALIGNED((*W));
     TORCH_CHECK(W->dim() == 2 && W->size(1) == E && W->device() == like.device(), "W [V, E] fp32 on the op's device");
     TORCH_CHECK(W->size(0) <= 0x7fffffffLL, "W: too many rows");
@@ -1111,6 +1125,7 @@ static std::vector<at::Tensor> reverse_step(const at::Tensor& like, int64_t N, i
   }
   TORCH_CHECK(bf == 0.f || xp, "reverse_step: b != 0 needs x");
   TORCH_CHECK(af == 0.f || pp || ip, "reverse_step: a != 0 needs pred or idx + W");
+  TORCH_CHECK(apf == 0.f || ppp || ipp, "reverse_step: a_prev != 0 needs pred_prev or idx_prev + W");
   TORCH_CHECK(!mp || xsp, "reverse_step: mask needs x_start");
   const c10::DeviceGuard guard(like.device());
   auto f32 = at::TensorOptions().device(like.device()).dtype(at::kFloat);
@@ -1120,7 +1135,7 @@ static std::vector<at::Tensor> reverse_step(const at::Tensor& like, int64_t N, i
     const bool ok = dpa::launch_reverse_step(
         xp, pp, ip, wp, xsp, mp, N, (int)E, (int)V, (float)scale, af, bf, sf, (uint64_t)seed, (uint32_t)step,
         (uint64_t)row_base, (float)tau, (float)erf_tau, out.data_ptr<float>(),
-        want_bf16 ? reinterpret_cast<uint16_t*>(out16.data_ptr()) : nullptr, cur_stream());
+        want_bf16 ? reinterpret_cast<uint16_t*>(out16.data_ptr()) : nullptr, cur_stream(), ppp, ipp, apf);
     TORCH_CHECK(ok, "reverse_step: unsupported arguments");
   }
   return {out, out16};
@@ -1404,12 +1419,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("emb_qsample_fwd", &emb_qsample_fwd,
         "DiffuSeq embedding gather + x_start noise + masked q_sample -> (x_start, x_start bf16, x_t bf16)");
   m.def("reverse_step", &reverse_step,
-        "DiffuSeq reverse update a x0 + b x + s z (in-kernel Philox noise; source rows kept) -> (out fp32, out bf16 | None)",
+        "DiffuSeq reverse update a x0 + a_prev x0_prev + b x + s z (in-kernel Philox noise; source rows kept) -> (out fp32, out bf16 | None)",
         py::arg("like"), py::arg("N"), py::arg("E"), py::arg("x") = py::none(), py::arg("pred") = py::none(),
         py::arg("idx") = py::none(), py::arg("W") = py::none(), py::arg("x_start") = py::none(),
         py::arg("mask") = py::none(), py::arg("scale") = 1.0, py::arg("a") = 0.0, py::arg("b") = 0.0,
         py::arg("s") = 0.0, py::arg("seed") = 0, py::arg("step") = 0, py::arg("row_base") = 0,
-        py::arg("tau") = 0.0, py::arg("erf_tau") = 0.0, py::arg("want_bf16") = false);
+        py::arg("tau") = 0.0, py::arg("erf_tau") = 0.0, py::arg("want_bf16") = false,
+        py::arg("pred_prev") = py::none(), py::arg("idx_prev") = py::none(), py::arg("a_prev") = 0.0);
   m.def("ngram_matches", &ngram_matches,
         "clipped 1..4-gram match counts of every sequence pair of a group -> int32 [G, K, K, 4] | None (shape not covered)",
         py::arg("tokens"), py::arg("lens"));

@@ -201,10 +201,15 @@ void launch_timestep_emb(const float* ts, int B, int dim, float max_period, uint
 // group index ((row_base + n) E + c) / 4, truncated to [-tau, tau] when tau > 0 (erf_tau =
 // erf(tau / sqrt 2)).  x may be null when b == 0, pred / idx / W when a == 0, mask / x_start and
 // out16 (the bf16 copy) always.  false: E % 4 != 0, N <= 0 or a required pointer is null.
+// a_prev != 0 (DPM-Solver++ 2M) adds a_prev x0_prev[n] on the same rows, x0_prev = pred_prev (bf16) or
+// scale * W[idx_prev[n]], and draws nothing; it needs one of the two (false otherwise).  a_prev == 0
+// is the three-term kernel, which reads neither: both may be null.
 bool launch_reverse_step(const float* x, const uint16_t* pred, const int64_t* idx, const float* W,
                          const float* x_start, const int64_t* mask, int64_t N, int E, int V, float scale,
                          float a, float b, float s, uint64_t seed, uint32_t step, uint64_t row_base,
-                         float tau, float erf_tau, float* out, uint16_t* out16, hipStream_t st);
+                         float tau, float erf_tau, float* out, uint16_t* out16, hipStream_t st,
+                         const uint16_t* pred_prev = nullptr, const int64_t* idx_prev = nullptr,
+                         float a_prev = 0.f);
 
 // ---- ngram_match.hip: clipped n-gram match counts of sequence pairs (MBR, BLEU) --------
 // m[g][i][j][n-1] = sum over the distinct n-grams y of min(count_i(y), count_j(y)), n = 1..4, for the

@@ -10,6 +10,13 @@
 // fp32 table, so the rounded [N, E] tensor never exists.  The output is written in fp32 (the
 // chain's state) and, on request, in bf16 (the next model input).
 //
+// The multistep DPM-Solver++ (2M) samplers add the previous update's x0_hat,
+//
+//   x_{t-1} = a x0_hat + a_prev x0_hat_prev + b x_t + s z
+//
+// from a second source of the same two kinds (PREV instantiations); it draws no noise.  Without
+// it (a_prev == 0) the kernel is the three-term one, instruction for instruction.
+//
 // Noise contract: z depends on (seed, step, global row, column) only.  One Philox block serves a
 // group of 4 columns; its key is (seed, step) and its counter the 64-bit global group index
 // ((row_base + n) E + c) / 4.  Nothing of the launch geometry, of the batch a row happens to be
@@ -57,14 +64,39 @@ __device__ __forceinline__ void rs_noise4(uint32_t seed_lo, uint32_t seed_hi, ui
   }
 }
 
-// x (b != 0), pred or idx + W (a != 0), mask + x_start and out16 are optional (null).
-template <bool TRUNC>
+// x0_hat of one 4-column group from its source: the bf16 prediction, else scale * W[idx[row]] (an
+// id outside [0, V): a zero row), else zero.
+__device__ __forceinline__ f32x4 rs_x0(const bf16_t* __restrict__ pred, const int64_t* __restrict__ idx,
+                                       const float* __restrict__ W, int64_t row, int g, int64_t o, int E, int V,
+                                       float scale) {
+  f32x4 x0 = {0.f, 0.f, 0.f, 0.f};
+  if (pred) {
+    const uint2 raw = *reinterpret_cast<const uint2*>(pred + o);
+    x0[0] = __uint_as_float(raw.x << 16);
+    x0[1] = __uint_as_float(raw.x & 0xffff0000u);
+    x0[2] = __uint_as_float(raw.y << 16);
+    x0[3] = __uint_as_float(raw.y & 0xffff0000u);
+  } else if (idx) {
+    const int64_t id = idx[row];
+    if (id >= 0 && id < V) {
+      const f32x4 w = *reinterpret_cast<const f32x4*>(W + id * E + g * 4);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) x0[k] = scale * w[k];
+    }
+  }
+  return x0;
+}
+
+// x (b != 0), pred or idx + W (a != 0), mask + x_start and out16 are optional (null).  PREV: the
+// launcher guarantees a_prev != 0 and pred_prev or idx_prev + W; otherwise the three are not read.
+template <bool TRUNC, bool PREV>
 __global__ void __launch_bounds__(256) reverse_step_kernel(
     const float* __restrict__ x, const bf16_t* __restrict__ pred, const int64_t* __restrict__ idx,
     const float* __restrict__ W, const float* __restrict__ x_start, const int64_t* __restrict__ mask,
     int64_t N, int E, int V, float scale, float a, float b, float s, uint32_t seed_lo, uint32_t seed_hi,
     uint32_t step, uint64_t row_base, float tau, float erf_tau, float* __restrict__ out,
-    bf16_t* __restrict__ out16) {
+    bf16_t* __restrict__ out16, const bf16_t* __restrict__ pred_prev, const int64_t* __restrict__ idx_prev,
+    float a_prev) {
   const int vpr = E >> 2;  // 16-byte vectors per row
   const int64_t n = N * vpr;
   for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n;
@@ -77,30 +109,21 @@ __global__ void __launch_bounds__(256) reverse_step_kernel(
       y = *reinterpret_cast<const f32x4*>(x_start + o);
     } else {
       f32x4 x0 = {0.f, 0.f, 0.f, 0.f}, xt = {0.f, 0.f, 0.f, 0.f};
-      if (a != 0.f) {
-        if (pred) {
-          const uint2 raw = *reinterpret_cast<const uint2*>(pred + o);
-          x0[0] = __uint_as_float(raw.x << 16);
-          x0[1] = __uint_as_float(raw.x & 0xffff0000u);
-          x0[2] = __uint_as_float(raw.y << 16);
-          x0[3] = __uint_as_float(raw.y & 0xffff0000u);
-        } else if (idx) {
-          const int64_t id = idx[row];
-          if (id >= 0 && id < V) {
-            const f32x4 w = *reinterpret_cast<const f32x4*>(W + id * E + g * 4);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) x0[k] = scale * w[k];
-          }
-        }
-      }
+      if (a != 0.f) x0 = rs_x0(pred, idx, W, row, g, o, E, V, scale);
       if (b != 0.f) xt = *reinterpret_cast<const f32x4*>(x + o);
       float z[4] = {0.f, 0.f, 0.f, 0.f};
       if (s != 0.f) {
         const uint64_t grp = (row_base + (uint64_t)row) * (uint64_t)vpr + (uint64_t)g;
         rs_noise4<TRUNC>(seed_lo, seed_hi, step, grp, tau, erf_tau, z);
       }
+      if (PREV) {
+        const f32x4 x0p = rs_x0(pred_prev, idx_prev, W, row, g, o, E, V, scale);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) y[k] = fmaf(a, x0[k], fmaf(b, xt[k], s * z[k]));
+        for (int k = 0; k < 4; ++k) y[k] = fmaf(a, x0[k], fmaf(a_prev, x0p[k], fmaf(b, xt[k], s * z[k])));
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) y[k] = fmaf(a, x0[k], fmaf(b, xt[k], s * z[k]));
+      }
     }
     *reinterpret_cast<f32x4*>(out + o) = y;
     if (out16) {
@@ -115,22 +138,22 @@ __global__ void __launch_bounds__(256) reverse_step_kernel(
 bool launch_reverse_step(const float* x, const uint16_t* pred, const int64_t* idx, const float* W,
                          const float* x_start, const int64_t* mask, int64_t N, int E, int V, float scale,
                          float a, float b, float s, uint64_t seed, uint32_t step, uint64_t row_base,
-                         float tau, float erf_tau, float* out, uint16_t* out16, hipStream_t st) {
+                         float tau, float erf_tau, float* out, uint16_t* out16, hipStream_t st,
+                         const uint16_t* pred_prev, const int64_t* idx_prev, float a_prev) {
   if (E <= 0 || E % 4 != 0 || N <= 0 || out == nullptr) return false;
   if (b != 0.f && x == nullptr) return false;
   if (a != 0.f && pred == nullptr && (idx == nullptr || W == nullptr)) return false;
+  if (a_prev != 0.f && pred_prev == nullptr && (idx_prev == nullptr || W == nullptr)) return false;
   if (mask != nullptr && x_start == nullptr) return false;
   int64_t g = (N * (E / 4) + 255) / 256;
   if (g > 256 * 16) g = 256 * 16;
   const uint32_t lo = (uint32_t)seed, hi = (uint32_t)(seed >> 32);
-  if (tau > 0.f)
-    hipLaunchKernelGGL(reverse_step_kernel<true>, dim3((unsigned)g), dim3(256), 0, st, x, (const bf16_t*)pred,
-                       idx, W, x_start, mask, N, E, V, scale, a, b, s, lo, hi, step, row_base, tau, erf_tau,
-                       out, (bf16_t*)out16);
-  else
-    hipLaunchKernelGGL(reverse_step_kernel<false>, dim3((unsigned)g), dim3(256), 0, st, x, (const bf16_t*)pred,
-                       idx, W, x_start, mask, N, E, V, scale, a, b, s, lo, hi, step, row_base, tau, erf_tau,
-                       out, (bf16_t*)out16);
+  const bool trunc = tau > 0.f, prev = a_prev != 0.f;  // a_prev == 0: the three-term kernel, no previous source read
+  auto kern = trunc ? (prev ? reverse_step_kernel<true, true> : reverse_step_kernel<true, false>)
+                    : (prev ? reverse_step_kernel<false, true> : reverse_step_kernel<false, false>);
+  hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(256), 0, st, x, (const bf16_t*)pred, idx, W, x_start, mask, N, E, V,
+                     scale, a, b, s, lo, hi, step, row_base, tau, erf_tau, out, (bf16_t*)out16,
+                     prev ? (const bf16_t*)pred_prev : nullptr, prev ? idx_prev : nullptr, a_prev);
   return true;
 }
 

@@ -190,11 +190,30 @@ class GaussianDiffusion:
             ddim(eta): sigma = eta sqrt((1 - ab_{i-1}) / (1 - ab_i)) sqrt(1 - ab_i / ab_{i-1}),
                        b = sqrt(max(1 - ab_{i-1} - sigma^2, 0)) / sqrt(1 - ab_i),
                        a = sqrt(ab_{i-1}) - b sqrt(ab_i), s = sigma
-            s = 0 at i = 0 (the last update adds no noise)."""
-        if sampler not in ("ancestral", "ddim"):
-            raise ValueError(f"unknown sampler {sampler!r} (ancestral or ddim)")
+            s = 0 at i = 0 (the last update adds no noise).
+
+        ``dpmpp_2m`` / ``dpmpp_2m_sde`` (the multistep DPM-Solver++ of DiffuSeq-v2; eta must be 0)
+        return 5-tuples (t_model, a, b, s, a_prev): the update is
+        ``x_prev = a x0_hat + a_prev x0_hat_prev + b x_t + s z`` with x0_hat_prev the prediction
+        of the update before.  With alpha_i = sqrt(ab_i), sigma_i = sqrt(1 - ab_i),
+        lambda_i = log(alpha_i / sigma_i) and h_i = lambda_{i-1} - lambda_i, for i >= 1
+
+            dpmpp_2m:     b = sigma_{i-1} / sigma_i,           A = -alpha_{i-1} expm1(-h_i),  s = 0
+            dpmpp_2m_sde: b = sigma_{i-1} / sigma_i e^{-h_i},  A = -alpha_{i-1} expm1(-2 h_i),
+                          s = sigma_{i-1} sqrt(-expm1(-2 h_i))
+            1 <= i <= S - 2 (second order), r = h_{i+1} / h_i:  a = A (1 + 1 / (2 r)), a_prev = -A / (2 r)
+            i = S - 1 (no history yet):                        a = A, a_prev = 0
+
+        and (a, b, s, a_prev) = (1, 0, 0, 0) at i = 0, the jump to sigma = 0.  (a + a_prev, b, s)
+        is the ddim update with eta = 0 / eta = 1."""
+        if sampler not in ("ancestral", "ddim", "dpmpp_2m", "dpmpp_2m_sde"):
+            raise ValueError(f"unknown sampler {sampler!r} (ancestral, ddim, dpmpp_2m or dpmpp_2m_sde)")
         kept = self.kept_timesteps(self.num_timesteps if steps is None else steps)
         ab = self.alphas_cumprod[kept]
+        if sampler.startswith("dpmpp_2m"):
+            if float(eta) != 0.0:
+                raise ValueError(f"sampler {sampler!r} takes no eta (got {eta})")
+            return self._dpmpp_2m_schedule(kept, ab, sde=sampler == "dpmpp_2m_sde")
         ab_prev = np.append(1.0, ab[:-1])
         beta = 1.0 - ab / ab_prev
         if sampler == "ancestral":
@@ -209,6 +228,26 @@ class GaussianDiffusion:
         s[0] = 0.0
         return [(int(kept[i]), float(a[i]), float(b[i]), float(s[i])) for i in reversed(range(len(kept)))]
 
+    @staticmethod
+    def _dpmpp_2m_schedule(kept, ab, sde):
+        """The 5-tuples of :meth:`reverse_schedule` for DPM-Solver++ (2M), float64; entry j of the
+        arrays below belongs to update i = j + 1."""
+        S = len(kept)
+        alpha, sigma = np.sqrt(ab), np.sqrt(1.0 - ab)
+        lam = np.log(alpha / sigma)
+        h = lam[:-1] - lam[1:]
+        e = np.expm1(-2.0 * h) if sde else np.expm1(-h)
+        A = -alpha[:-1] * e
+        b = sigma[:-1] / sigma[1:] * (np.exp(-h) if sde else 1.0)
+        s = sigma[:-1] * np.sqrt(-e) if sde else np.zeros_like(h)
+        a, a_prev = A.copy(), np.zeros_like(A)
+        half_inv_r = 0.5 * h[:-1] / h[1:]  # 1 / (2 r_i), i = 1 .. S - 2; update S - 1 stays first order
+        a[:-1] = A[:-1] * (1.0 + half_inv_r)
+        a_prev[:-1] = -A[:-1] * half_inv_r
+        rows = [(int(kept[i]), float(a[i - 1]), float(b[i - 1]), float(s[i - 1]), float(a_prev[i - 1]))
+                for i in reversed(range(1, S))]
+        return rows + [(int(kept[0]), 1.0, 0.0, 0.0, 0.0)]
+
     @torch.no_grad()
     def _reverse_loop(self, model, net, x_start, mask, sched, clamp_step, c, *, generator, noise_seed,
                       row_base, top_p):
@@ -216,7 +255,10 @@ class GaussianDiffusion:
         ``noise_seed`` the noise is the op's own (on a GPU: drawn inside the fused kernel, keyed
         by (noise_seed, position in the chain, row_base + row)), a rounded prediction reaches the
         op as token ids + the embedding table, the model reads the op's bf16 output, and nothing
-        in the loop synchronises with the host.  Otherwise the noise comes from ``generator``."""
+        in the loop synchronises with the host.  Otherwise the noise comes from ``generator``.
+        A 5-tuple schedule (the multistep samplers) keeps each update's x0 source - the prediction
+        tensor or the rounded ids, whichever the update read - and hands it to the next update
+        whose ``a_prev`` is not zero."""
         from ..ops import diffusion as dops
         seeded = noise_seed is not None
         dev, B, S = x_start.device, x_start.shape[0], len(sched)
@@ -230,7 +272,8 @@ class GaussianDiffusion:
         # step ids: S for the start noise (never truncated: DiffuSeq's top_p acts on the steps'
         # noise only), then the chain position S - 1 .. 0
         x, x16 = dops.reverse_step(None, a=0.0, b=0.0, s=1.0, step=S, noise=noise(0.0), want_bf16=want16, **kw)
-        for j, (k, a, b, s) in enumerate(sched):
+        prev = None  # (keyword, tensor) of the update before, multistep schedules only
+        for j, (k, a, b, s, *more) in enumerate(sched):
             t = torch.full((B,), k, dtype=torch.long, device=dev)
             pred = model(x if x16 is None else x16, self.scale_timesteps(t))
             if not seeded:
@@ -238,8 +281,12 @@ class GaussianDiffusion:
             src = dict(pred=pred)
             if clamp_step is None or k <= clamp_step:
                 src = dict(idx=net.nearest_tokens(pred, c), weight=W, scale=scale)
+            if more and more[0] != 0.0:
+                src.update({prev[0] + "_prev": prev[1], "a_prev": more[0], "weight": W, "scale": scale})
             x, x16 = dops.reverse_step(x, a=a, b=b, s=s, step=S - 1 - j, top_p=top_p,
                                        noise=noise(top_p) if s != 0.0 else None, want_bf16=want16, **src, **kw)
+            if more:
+                prev = ("idx", src["idx"]) if "idx" in src else ("pred", pred)
         return x
 
     @torch.no_grad()
@@ -250,7 +297,9 @@ class GaussianDiffusion:
         embeddings; every predicted x_0 (at the steps t <= clamp_step, an original timestep;
         None: all) is rounded to its nearest word embedding.
 
-        steps / sampler / eta: the chain of :meth:`reverse_schedule` (None: all T steps).
+        steps / sampler / eta: the chain of :meth:`reverse_schedule` (None: all T steps).  The
+        multistep samplers ``dpmpp_2m`` / ``dpmpp_2m_sde`` reuse the previous update's (rounded)
+        prediction, at no extra forward; they take eta = 0.
         top_p = tau > 0: every step's noise is truncated to [-tau, tau].  noise_seed (int): the
         noise is keyed by (noise_seed, step, row_base + sample row, column) instead of coming from
         ``generator``, so a sample decodes to the same result in whatever batch it is placed

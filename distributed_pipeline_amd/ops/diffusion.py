@@ -12,7 +12,8 @@ Fused DiffuSeq diffusion-side ops on the gfx950 kernels of ``csrc/diffusion.hip`
   the backward writes d(model output) in its dtype and d(x_start) in fp32.
 * :func:`timestep_embedding` - sinusoidal [cos | sin] embedding straight to bf16.
 * :func:`reverse_step` - one reverse-process update of decoding,
-  ``a x0_hat + b x_t + s z`` with the source rows kept, as one kernel
+  ``a x0_hat + b x_t + s z`` (+ ``a_prev x0_hat_prev`` for the multistep
+  samplers) with the source rows kept, as one kernel
   (``csrc/reverse_step.hip``) with batch-independent in-kernel noise; it carries
   its own PyTorch path for the CPU / fp32.
 
@@ -145,7 +146,8 @@ def draw_noise(shape, device, generator, top_p=0.0):
 
 
 def reverse_step(x, *, pred=None, idx=None, weight=None, scale=1.0, x_start=None, mask=None, a, b, s,
-                 seed, step, row_base=0, top_p=0.0, noise=None, want_bf16=False):
+                 seed, step, row_base=0, top_p=0.0, noise=None, want_bf16=False,
+                 pred_prev=None, idx_prev=None, a_prev=0.0):
     """One DiffuSeq reverse-process update ``[..., E]`` -> ``(out fp32, out bf16 | None)``:
 
         x0  = pred                          (the model's prediction)
@@ -159,7 +161,16 @@ def reverse_step(x, *, pred=None, idx=None, weight=None, scale=1.0, x_start=None
     whose z depends on (seed, step, row_base + row, column) only - not on the batch a row is in -
     and is truncated to [-top_p, top_p] when top_p > 0.  Anything else evaluates the same formula
     in fp32 PyTorch with ``noise`` or, without it, noise from a generator seeded with
-    (seed, step): the same distribution, other bits, reproducible for the same batch."""
+    (seed, step): the same distribution, other bits, reproducible for the same batch.
+
+    The multistep samplers (DPM-Solver++ 2M) add the previous update's x0 with ``a_prev != 0``:
+
+        x0p = pred_prev  or  scale * weight[idx_prev]    (``weight`` and ``scale`` are shared with idx)
+        y   = a * x0 + a_prev * x0p + b * x + s * z
+
+    in the same kernel (a bf16 ``pred_prev`` or ids into the fp32 ``weight``; the two sources need
+    not be of one kind); the term draws no noise.  With ``a_prev == 0`` the previous source is
+    not looked at and the result is the three-term update's, bit for bit."""
     ref = next((t for t in (x, pred, x_start) if t is not None), None)
     if ref is None:
         raise ValueError("reverse_step: one of x, pred, x_start must be given (it fixes the shape)")
@@ -167,30 +178,45 @@ def reverse_step(x, *, pred=None, idx=None, weight=None, scale=1.0, x_start=None
         raise ValueError("reverse_step: idx needs weight")
     if mask is not None and x_start is None:
         raise ValueError("reverse_step: mask needs x_start")
-    a, b, s = float(a), float(b), float(s)
+    a, b, s, a_prev = float(a), float(b), float(s), float(a_prev)
     if (b != 0.0 and x is None) or (a != 0.0 and pred is None and idx is None):
         raise ValueError("reverse_step: b != 0 needs x, a != 0 needs pred or idx")
+    if a_prev == 0.0:
+        pred_prev = idx_prev = None
+    elif pred_prev is None and idx_prev is None:
+        raise ValueError("reverse_step: a_prev != 0 needs pred_prev or idx_prev")
+    elif pred_prev is None and weight is None:
+        raise ValueError("reverse_step: idx_prev needs weight")
     shape, dev = ref.shape, ref.device
     E = int(shape[-1])
-    if _kernel_ok(dev, E, x, pred, idx, weight, x_start, noise):
+    if _kernel_ok(dev, E, x, pred, idx, weight, x_start, noise) and _source_ok(pred_prev, idx_prev, weight):
         N = ref.numel() // E
         m = None if mask is None else mask.reshape(-1).to(torch.long).contiguous()
         ids = None if idx is None or pred is not None else idx.reshape(-1).to(torch.long).contiguous()
+        hist = {}
+        if a_prev != 0.0:
+            hist = dict(a_prev=a_prev, pred_prev=_c(pred_prev),
+                        idx_prev=None if pred_prev is not None else idx_prev.reshape(-1).to(torch.long).contiguous())
+        gathers = ids is not None or hist.get("idx_prev") is not None
         out, out16 = get_ext().reverse_step(
-            ref, N, E, x=_c(x), pred=_c(pred), idx=ids, W=None if ids is None else weight.detach().contiguous(),
+            ref, N, E, x=_c(x), pred=_c(pred), idx=ids, W=weight.detach().contiguous() if gathers else None,
             x_start=_c(x_start), mask=m, scale=float(scale),
             a=a, b=b, s=s, seed=int(seed), step=int(step), row_base=int(row_base), tau=max(float(top_p), 0.0),
-            erf_tau=_erf_tau(top_p) if top_p > 0 else 0.0, want_bf16=bool(want_bf16))
+            erf_tau=_erf_tau(top_p) if top_p > 0 else 0.0, want_bf16=bool(want_bf16), **hist)
         return out.view(shape), (out16.view(shape) if want_bf16 else None)
+
+    def source(p, i):
+        if p is not None:
+            return p.float()
+        V = weight.shape[0]
+        ok = (i >= 0) & (i < V)
+        return float(scale) * weight.detach().float()[i.clamp(0, V - 1)] * ok.unsqueeze(-1)
+
     y = torch.zeros(shape, dtype=torch.float32, device=dev)
     if a != 0.0:
-        if pred is not None:
-            x0 = pred.float()
-        else:
-            V = weight.shape[0]
-            ok = (idx >= 0) & (idx < V)
-            x0 = float(scale) * weight.detach().float()[idx.clamp(0, V - 1)] * ok.unsqueeze(-1)
-        y = y + a * x0
+        y = y + a * source(pred, idx)
+    if a_prev != 0.0:
+        y = y + a_prev * source(pred_prev, idx_prev)
     if b != 0.0:
         y = y + b * x.float()
     if s != 0.0:
@@ -202,15 +228,19 @@ def reverse_step(x, *, pred=None, idx=None, weight=None, scale=1.0, x_start=None
     return y, (y.to(torch.bfloat16) if want_bf16 else None)
 
 
+def _source_ok(pred, idx, weight):
+    """An x0 source the kernel reads: a bf16 prediction, or ids into an fp32 table (or none)."""
+    if pred is not None:
+        return pred.dtype == torch.bfloat16
+    return idx is None or weight.dtype == torch.float32
+
+
 def _kernel_ok(dev, E, x, pred, idx, weight, x_start, noise):
     if dev.type != "cuda" or noise is not None or E % 4 != 0:
         return False
     if any(t is not None and t.dtype != torch.float32 for t in (x, x_start)):
         return False
-    if pred is not None:
-        if pred.dtype != torch.bfloat16:
-            return False
-    elif idx is not None and weight.dtype != torch.float32:
+    if not _source_ok(pred, idx, weight):
         return False
     ext = get_ext()
     if ext is None:

@@ -13,7 +13,9 @@ a ``vocab.txt``.
 generator seeded with ``seed``.
 
 ``--step S`` decodes with a respaced chain of S steps, ``--sampler ddim --ddim_eta`` with DDIM
-updates, ``--top_p`` truncates every step's noise, and ``--mbr K`` decodes K candidates per source
+updates, ``--sampler dpmpp_2m`` / ``dpmpp_2m_sde`` with the second-order multistep DPM-Solver++
+(deterministic / with noise; each update also reads the previous step's prediction, no extra
+forward; ``--ddim_eta`` must stay 0), ``--top_p`` truncates every step's noise, and ``--mbr K`` decodes K candidates per source
 and writes their minimum-Bayes-risk pick (``--keep_candidates true``: all of them too; the pick of
 a whole batch is one n-gram match kernel on the device, ``utils.mbr.mbr_select_batch``;
 ``--mbr_metric rouge_l`` picks by ROUGE-L instead of BLEU, on one LCS kernel).  With
@@ -114,6 +116,8 @@ def recover_parts(recs, mask, pad_id=0):
 
 def main(namespace):
     args: SampleSettings = SampleSettings.from_argparse(namespace)
+    if args.sampler.startswith("dpmpp_2m") and args.ddim_eta != 0.0:
+        raise ValueError(f"--ddim_eta {args.ddim_eta} does not apply to --sampler {args.sampler}: leave it at 0")
 
     import torch
 

@@ -8,6 +8,9 @@ Both sides start from the same bf16 model output (and, on the rounded steps, the
 the arg-max of the rounding is common to both and left out) and end with the fp32 x_{t-1} and
 its bf16 copy, the next forward's input.  The chain is the real ``p_sample`` around a stub model
 that does the input cast of ``TransformerNetModel.forward`` and returns the fixed prediction.
+The four-term update of the multistep samplers (``a_prev`` times the previous step's prediction,
+``fused4_*``) is timed next to the three-term one and next to a composition of the three-term
+kernel and a PyTorch ``add_`` (``fused3_plus_add_*``).
 Every variant of a shape is timed in turn inside each repetition (interleaved); a repetition is
 ``inner`` back-to-back calls between two device events; medians and min-max over the repetitions.
 """
@@ -81,15 +84,45 @@ def shape(N, L, E, V, reps):
         return lambda: dops.reverse_step(x, x_start=x_start, mask=mask, a=a, b=b, s=s, seed=1, step=1000,
                                          top_p=top_p, want_bf16=True, **src)
 
+    # the multistep (DPM-Solver++ 2M) update: the previous step's prediction as a fourth term, in the
+    # same kernel, or added by a PyTorch add_ to the three-term kernel's output (two launches, after
+    # a gather on the rounded steps).  The composition is timed as a lower bound of what it would
+    # cost: it neither keeps the source rows at x_start nor refreshes the bf16 copy.
+    prev16 = torch.randn(B, L, E, device="cuda", generator=g).bfloat16()
+    idx_prev = torch.randint(0, V, (B, L), device="cuda", generator=g)
+    _, a4, b4, s4, a_prev = diff.reverse_schedule(4, "dpmpp_2m_sde")[1]
+
+    def four(rounded):
+        src = dict(idx=idx, idx_prev=idx_prev, weight=W) if rounded else dict(pred=pred16, pred_prev=prev16)
+        return lambda: dops.reverse_step(x, x_start=x_start, mask=mask, a=a4, b=b4, s=s4, a_prev=a_prev, seed=1,
+                                         step=1000, want_bf16=True, **src)
+
+    def two_launch(rounded):
+        three = fused(0.0, rounded)
+
+        def run():
+            y, _ = three()
+            return y.add_(torch.nn.functional.embedding(idx_prev, W) if rounded else prev16, alpha=a_prev)
+        return run
+
     inner = 200 if N >= 65536 else 1000  # every window is tens of milliseconds of device work
     out = interleaved({
         "chain_unrounded": (chain(None), inner),
         "fused_unrounded": (fused(0.0, False), inner),
         "fused_unrounded_top_p0.9": (fused(0.9, False), inner),
+        "fused4_unrounded": (four(False), inner),
+        "fused3_plus_add_unrounded": (two_launch(False), inner),
         "chain_rounded": (chain(gather), inner),
         "fused_rounded": (fused(0.0, True), inner),
         "fused_rounded_top_p0.9": (fused(0.9, True), inner),
+        "fused4_rounded": (four(True), inner),
+        "fused3_plus_add_rounded": (two_launch(True), inner),
     }, reps)
+    for kind in ("unrounded", "rounded"):
+        out[f"fused4_{kind}"]["vs_three_term"] = round(
+            out[f"fused4_{kind}"]["median_ms"] / out[f"fused_{kind}"]["median_ms"], 3)
+        out[f"fused3_plus_add_{kind}"]["vs_four_term"] = round(
+            out[f"fused3_plus_add_{kind}"]["median_ms"] / out[f"fused4_{kind}"]["median_ms"], 3)
     # bytes the update needs: x_t, x_start on the source half, the prediction (bf16) or the
     # gathered rows (fp32) on the target half, both outputs
     tgt = float((mask != 0).float().mean())
@@ -99,6 +132,11 @@ def shape(N, L, E, V, reps):
         for name in (f"fused_{kind}", f"fused_{kind}_top_p0.9"):
             out[name]["needed_GBps"] = round(need[kind] / out[name]["median_ms"] / 1e6, 1)
             out[name]["speedup_vs_chain"] = round(out[f"chain_{kind}"]["median_ms"] / out[name]["median_ms"], 2)
+    # the fourth term reads one more source on the target half: bf16, or gathered fp32 rows
+    need4 = {"unrounded": need["unrounded"] + N * E * 2 * tgt, "rounded": need["rounded"] + N * E * 4 * tgt}
+    for kind in need4:
+        out[f"fused4_{kind}"]["needed_GBps"] = round(need4[kind] / out[f"fused4_{kind}"]["median_ms"] / 1e6, 1)
+        out[f"fused4_{kind}"]["needed_bytes_vs_three_term"] = round(need4[kind] / need[kind], 3)
     return {"N": N, "L": L, "E": E, "V": V, "target_fraction": tgt, **out}
 
 
