@@ -16,6 +16,9 @@ class EvalSettings(S):
     rouge_l: bool \
         = _(False, "Also report `rouge_l` (mean ROUGE-L of recover against reference) and, for rows with "
                    "candidates, `self_rouge_l`.")
+    diversity: bool \
+        = _(False, "Also report `dist2`, `dist3`, `dist4` (mean distinct n-grams / n-grams of recover) and, "
+                   "for rows with candidates, `div4` (distinct 4-grams of a row's candidates / their 4-grams).")
 
 
 __all__ = ('EvalSettings',)

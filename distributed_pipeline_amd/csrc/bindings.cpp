@@ -1163,6 +1163,28 @@ static c10::optional<at::Tensor> ngram_matches(const at::Tensor& tokens, const a
   return m;
 }
 
+// Distinct n-gram counts of a group's K sequences and of their union (csrc/ngram_distinct.hip):
+// tokens [G, K, L] int32 / int64, lens [G, K] int32 -> int32 [G, K + 1, 4], or None for a shape the
+// kernel does not cover.
+static c10::optional<at::Tensor> ngram_distinct(const at::Tensor& tokens, const at::Tensor& lens) {
+  CHECK_DEV(tokens); CHECK_CONTIG(tokens); CHECK_DEV(lens); CHECK_CONTIG(lens);
+  TORCH_CHECK(tokens.scalar_type() == at::kInt || tokens.scalar_type() == at::kLong,
+              "ngram_distinct: tokens must be int32 or int64");
+  TORCH_CHECK(lens.scalar_type() == at::kInt, "ngram_distinct: lens must be int32");
+  TORCH_CHECK(tokens.dim() == 3 && lens.dim() == 2 && lens.size(0) == tokens.size(0) &&
+                  lens.size(1) == tokens.size(1) && lens.device() == tokens.device(),
+              "ngram_distinct: tokens [G, K, L], lens [G, K] on one device");
+  const int64_t G = tokens.size(0), K = tokens.size(1), L = tokens.size(2);
+  const c10::DeviceGuard guard(tokens.device());
+  at::Tensor d = at::empty({G, K + 1, 4}, tokens.options().dtype(at::kInt));
+  if (G == 0) return d;
+  if (K > 0x7fffffffLL || L > 0x7fffffffLL) return c10::nullopt;
+  if (!dpa::launch_ngram_distinct(tokens.data_ptr(), tokens.scalar_type() == at::kLong, lens.data_ptr<int>(), G,
+                                  (int)K, (int)L, d.data_ptr<int>(), cur_stream()))
+    return c10::nullopt;
+  return d;
+}
+
 // LCS length of every pair of a group's K sequences (csrc/lcs.hip): tokens [G, K, L] int32 / int64,
 // lens [G, K] int32 -> int32 [G, K, K], or None for a shape the kernel does not cover.
 static c10::optional<at::Tensor> lcs_lengths(const at::Tensor& tokens, const at::Tensor& lens) {
@@ -1428,6 +1450,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("pred_prev") = py::none(), py::arg("idx_prev") = py::none(), py::arg("a_prev") = 0.0);
   m.def("ngram_matches", &ngram_matches,
         "clipped 1..4-gram match counts of every sequence pair of a group -> int32 [G, K, K, 4] | None (shape not covered)",
+        py::arg("tokens"), py::arg("lens"));
+  m.def("ngram_distinct", &ngram_distinct,
+        "distinct 1..4-gram counts of every sequence of a group and of their union -> int32 [G, K + 1, 4] | None (shape not covered)",
         py::arg("tokens"), py::arg("lens"));
   m.def("lcs_lengths", &lcs_lengths,
         "longest-common-subsequence length of every sequence pair of a group -> int32 [G, K, K] | None (shape not covered)",

@@ -219,6 +219,14 @@ bool launch_reverse_step(const float* x, const uint16_t* pred, const int64_t* id
 bool launch_ngram_match(const void* tokens, bool tok64, const int* lens, int64_t G, int K, int L, int* m,
                         hipStream_t st);
 
+// ---- ngram_distinct.hip: distinct n-gram counts per sequence and per group (dist-n, div-n) ----
+// d[g][k][n-1] = number of distinct n-grams of tokens[g][k][0 .. lens[g][k]) for k < K, d[g][K][n-1] =
+// number of distinct n-grams of the union of the group's K sequences, n = 1..4 (the conventions of
+// launch_ngram_match; d int32 [G, K + 1, 4]).  Exact integers, no global atomics.  false, with no
+// launch: a shape outside 1 <= K <= 16, 1 <= L <= 256, 1 <= G < 2^31, or a null pointer.
+bool launch_ngram_distinct(const void* tokens, bool tok64, const int* lens, int64_t G, int K, int L, int* d,
+                           hipStream_t st);
+
 // ---- lcs.hip: longest-common-subsequence lengths of sequence pairs (ROUGE-L) ------------
 // out[g][i][j] = LCS length of tokens[g][i][0 .. lens[g][i]) and tokens[g][j][0 .. lens[g][j]) (ids
 // there in [0, 2^31); lens clamped to [0, L]; int32 or int64 ids; out int32 [G, K, K]).  Exact
