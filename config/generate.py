@@ -1,0 +1,92 @@
+"""
+Generation settings (L4) for ``python -m run.generate``.
+
+The model and data groups are the training ones, so the ``training_args.json`` a GPT-2 training
+run writes next to its checkpoints is a valid ``--config_json`` here, through the key filtering of
+``config/sample.py``: keys that only training reads are dropped, anything else unknown is still
+rejected, and flags given on the command line are applied on top of the JSON.
+"""
+from typing import final
+from argparse import ArgumentParser as Ap, ArgumentDefaultsHelpFormatter as Df
+
+from .base import S, Choice, Item as _
+from .sample import SampleSettings
+from .train import DataSettings, ModelSettings
+
+
+class ContinueSettings(S):
+    model_path: str \
+        = _("", "Checkpoint file, or a checkpoint directory: its newest ema_<use_ema>_NNNNNN.pt if use_ema "
+                "is set, else its newest model_NNNNNN.pt.")
+    use_ema: str \
+        = _("", "EMA rate (e.g. 0.9999) whose weights to generate with when model_path is a directory.")
+    split: str \
+        = _("test", "Dataset split the prompts come from.")
+    batch_size: int \
+        = _(64, "Prompts per batch.")
+    num_batches: int \
+        = _(1, "Batches to continue.")
+    prompt_len: int \
+        = _(32, "Prompt: the first prompt_len tokens of each input_ids row.")
+    max_new_tokens: int \
+        = _(64, "Tokens to generate per prompt; prompt_len + max_new_tokens <= seq_len.")
+    temperature: float \
+        = _(1.0, "Softmax temperature; 0 = greedy (arg-max, ties to the lowest id).")
+    top_k: int \
+        = _(0, "Sample among the k most likely tokens (and ties with the k-th); 0 = off.")
+    top_p: float \
+        = _(0.0, "Nucleus sampling: the smallest set of most likely tokens whose mass reaches top_p; 0 = off.")
+    eos_id: int \
+        = _(-1, "Token id that ends a continuation; -1 = none.")
+    seed: int \
+        = _(102, "Sampling seed.")
+    out_path: str \
+        = _("", "Output .jsonl file (default: generated_<checkpoint>_seed<seed>.jsonl next to the checkpoint).")
+    precision: Choice("bf16", "fp32") \
+        = _("bf16", "Compute precision the model was trained with.")
+    use_hip_kernels: bool \
+        = _(True, "Use the hand-written gfx950 kernels (required on GPU).")
+
+
+@final
+class GenerateSettings(
+        ContinueSettings,
+        ModelSettings,
+        DataSettings
+):
+
+    @classmethod
+    def to_argparse(cls, parser_or_group=None, add_json=False):
+        if not add_json:
+            return super(GenerateSettings, cls).to_argparse(parser_or_group)
+        if parser_or_group is None:
+            parser_or_group = Ap(formatter_class=Df)
+        setting_group = parser_or_group.add_argument_group(title="settings")
+        setting_group.add_argument(
+            "--config_json", type=str, required=False,
+            help="Load settings from this JSON file (a training config works); flags given explicitly "
+                 "override it.")
+        super(GenerateSettings, cls).to_argparse(setting_group, _suppress_defaults=True)
+        return parser_or_group
+
+    # the JSON loading and train-only key filtering of run.sample's settings, on this class's fields
+    from_argparse = classmethod(SampleSettings.from_argparse.__func__)
+
+    def check(self):
+        """Reject what no checkpoint could make sense of (before one is read)."""
+        if self.model != "gpt2":
+            raise ValueError(f"run.generate continues prompts with the gpt2 model, not {self.model!r}")
+        if not 0.0 <= self.top_p <= 1.0:
+            raise ValueError(f"--top_p must be in [0, 1], got {self.top_p}")
+        if self.temperature < 0:
+            raise ValueError(f"--temperature must be >= 0, got {self.temperature}")
+        if self.top_k < 0:
+            raise ValueError(f"--top_k must be >= 0, got {self.top_k}")
+        if self.prompt_len < 1 or self.max_new_tokens < 1:
+            raise ValueError("--prompt_len and --max_new_tokens must be >= 1")
+        if self.prompt_len + self.max_new_tokens > self.seq_len:
+            raise ValueError(f"--prompt_len {self.prompt_len} + --max_new_tokens {self.max_new_tokens} exceeds "
+                             f"seq_len {self.seq_len}")
+
+
+__all__ = ('GenerateSettings', 'ContinueSettings')

@@ -1,0 +1,231 @@
+// GPT-2 generation: the KV-cache append and the single-query attention of one decode step as one
+// kernel.
+//
+//   qkv_new [B][3][H][D] bf16   the new token's packed projection (rows qkv_stride apart)
+//   k_cache / v_cache           bf16 rows of D at (b, h, key): base + b * sb + h * sh + key * D
+//   lens [B] int32              keys already cached per row, before the call (not modified)
+//   out [B][H][D] bf16          softmax(q K^T / sqrt D) V over the keys 0 .. lens[b], rounded once
+//
+// A row with 0 <= lens[b] < Lmax stores the new k and v (the bits of qkv_new) at cache row lens[b]
+// and attends over the lens[b] cached keys plus the new one, which is taken from registers and
+// never re-read.  Any other lens[b] marks an inactive (parked) row: nothing is stored and its out
+// row is zeros.  Cache rows at or beyond lens[b] are never loaded, whatever they hold.
+//
+// The step is a memory-bound read of 2 * len * D * 2 bytes per (b, h) at one query row, so there
+// is nothing for the matrix cores and nothing to share through LDS: one workgroup of 4 waves per
+// (b, h); D / 8 lanes own a key row in 16-byte loads, so one wave load covers KPW = 512 / D whole
+// keys (1 KB, contiguous); a wave takes U = 4 such loads of K and of V (U * KPW consecutive keys)
+// per iteration and issues the next iteration's loads before it computes on this one's (two
+// register sets, ping-pong).  Each lane group keeps an fp32 online-softmax triple (m, l, o slice)
+// in the exp2 domain; probabilities and the PV sum stay in fp32 on the VALU.  The lane groups of a
+// wave merge by shuffles, the four waves once through 4 * (D + 2) floats of LDS.  No atomics, one
+// writer per output element: results are bitwise reproducible.
+//
+// The grid is B * H workgroups; there is no split over keys across workgroups, so a small batch
+// does not fill the chip.
+#include <math.h>
+
+#include "common.h"
+#include "launchers.h"
+
+namespace dpa {
+
+constexpr int AD_U = 4;      // wave loads of K (and of V) in flight per register set
+constexpr int AD_WAVES = 4;
+
+__device__ __forceinline__ void ad_unpack8(const uint4 r, float f[8]) {
+  f[0] = __uint_as_float(r.x << 16); f[1] = __uint_as_float(r.x & 0xffff0000u);
+  f[2] = __uint_as_float(r.y << 16); f[3] = __uint_as_float(r.y & 0xffff0000u);
+  f[4] = __uint_as_float(r.z << 16); f[5] = __uint_as_float(r.z & 0xffff0000u);
+  f[6] = __uint_as_float(r.w << 16); f[7] = __uint_as_float(r.w & 0xffff0000u);
+}
+
+// this lane group's running (m, l, o[8]); m in the exp2 domain, -inf while the group has no key
+struct AdState {
+  float m, l, o[8];
+};
+
+// q . k over the G lanes of a group (every lane of the group gets the sum)
+template <int G>
+__device__ __forceinline__ float ad_dot(const float q[8], const uint4 kr) {
+  float kf[8];
+  ad_unpack8(kr, kf);
+  float d = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) d = fmaf(q[i], kf[i], d);
+#pragma unroll
+  for (int off = G >> 1; off > 0; off >>= 1) d += __shfl_xor(d, off, 64);
+  return d;
+}
+
+// fold N scored keys (s[u] = -inf: not a key) with their V slices into the state
+template <int N>
+__device__ __forceinline__ void ad_update(AdState& st, const float s[N], const uint4 vr[N]) {
+  float mx = s[0];
+#pragma unroll
+  for (int u = 1; u < N; ++u) mx = fmaxf(mx, s[u]);
+  const float mn = fmaxf(st.m, mx);
+  const float ms = mn == -INFINITY ? 0.f : mn;  // no key yet: every exponent below is -inf, never NaN
+  const float alpha = fexp2(st.m - ms);
+  st.l *= alpha;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) st.o[i] *= alpha;
+#pragma unroll
+  for (int u = 0; u < N; ++u) {
+    const float p = fexp2(s[u] - ms);
+    float vf[8];
+    ad_unpack8(vr[u], vf);
+    st.l += p;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) st.o[i] = fmaf(p, vf[i], st.o[i]);
+  }
+  st.m = mn;
+}
+
+template <int D>
+__global__ void __launch_bounds__(64 * AD_WAVES) attn_decode_kernel(
+    const bf16_t* __restrict__ qkv, int64_t qkv_stride, bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
+    int64_t k_sb, int64_t k_sh, int64_t v_sb, int64_t v_sh, const int* __restrict__ lens, int H, int Lmax,
+    bf16_t* __restrict__ out) {
+  constexpr int G = D / 8;               // lanes per key row
+  constexpr int KPW = 64 / G;            // keys per wave load
+  constexpr int U = AD_U;
+  constexpr int WK = U * KPW;            // keys per wave per iteration
+  constexpr int IT = AD_WAVES * WK;      // keys per workgroup iteration
+  __shared__ float sm_o[AD_WAVES][D];
+  __shared__ float sm_ml[AD_WAVES][2];
+
+  const int b = blockIdx.x / H, h = blockIdx.x - b * H;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = lane / G, c = lane - g * G;
+  const int n = lens[b];  // cached keys; the new one becomes key n
+  bf16_t* orow = out + ((int64_t)b * H + h) * D;
+  if (n < 0 || n >= Lmax) {  // inactive row (uniform over the workgroup)
+    if (tid < D / 2) reinterpret_cast<uint32_t*>(orow)[tid] = 0u;
+    return;
+  }
+
+  const bf16_t* qrow = qkv + (int64_t)b * qkv_stride + (int64_t)h * D + c * 8;
+  const uint4 qraw = *reinterpret_cast<const uint4*>(qrow);
+  const uint4 knew = *reinterpret_cast<const uint4*>(qrow + (int64_t)H * D);
+  const uint4 vnew = *reinterpret_cast<const uint4*>(qrow + 2 * (int64_t)H * D);
+  const bf16_t* kb = kc + (int64_t)b * k_sb + (int64_t)h * k_sh + c * 8;
+  const bf16_t* vb = vc + (int64_t)b * v_sb + (int64_t)h * v_sh + c * 8;
+  if (wave == 0 && g == 0) {  // the append: n < Lmax
+    *reinterpret_cast<uint4*>(kc + (int64_t)b * k_sb + (int64_t)h * k_sh + (int64_t)n * D + c * 8) = knew;
+    *reinterpret_cast<uint4*>(vc + (int64_t)b * v_sb + (int64_t)h * v_sh + (int64_t)n * D + c * 8) = vnew;
+  }
+
+  float q[8];
+  ad_unpack8(qraw, q);
+  constexpr float qscale = (D == 64 ? 0.125f : 0.08838834764831845f) * LOG2E;  // 1 / sqrt D, exp2 domain
+#pragma unroll
+  for (int i = 0; i < 8; ++i) q[i] *= qscale;
+
+  AdState st;
+  st.m = -INFINITY;
+  st.l = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) st.o[i] = 0.f;
+
+  // keys base + u * KPW + g, u < U, of this wave; rows >= n are not loaded
+  auto load = [&](int base, uint4 kr[U], uint4 vr[U]) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int key = base + u * KPW + g;
+      kr[u] = make_uint4(0u, 0u, 0u, 0u);
+      vr[u] = make_uint4(0u, 0u, 0u, 0u);
+      if (key < n) {
+        kr[u] = *reinterpret_cast<const uint4*>(kb + (int64_t)key * D);
+        vr[u] = *reinterpret_cast<const uint4*>(vb + (int64_t)key * D);
+      }
+    }
+  };
+  auto fold = [&](int base, const uint4 kr[U], const uint4 vr[U]) {
+    float s[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const float d = ad_dot<G>(q, kr[u]);
+      s[u] = (base + u * KPW + g < n) ? d : -INFINITY;
+    }
+    ad_update<U>(st, s, vr);
+  };
+
+  int base = wave * WK;  // wave-uniform, as is every branch on it
+  if (base < n) {
+    uint4 ka[U], va[U], kb2[U], vb2[U];
+    load(base, ka, va);
+    for (;;) {
+      if (base + IT < n) load(base + IT, kb2, vb2);
+      fold(base, ka, va);
+      base += IT;
+      if (base >= n) break;
+      if (base + IT < n) load(base + IT, ka, va);
+      fold(base, kb2, vb2);
+      base += IT;
+      if (base >= n) break;
+    }
+  }
+
+  {  // the new key, from registers: group 0 of wave 0 takes it
+    const float d = ad_dot<G>(q, knew);
+    const float s[1] = {(wave == 0 && g == 0) ? d : -INFINITY};
+    const uint4 v1[1] = {vnew};
+    ad_update<1>(st, s, v1);
+  }
+
+  // merge the wave's lane groups (same d slice, different keys)
+#pragma unroll
+  for (int off = G; off < 64; off <<= 1) {
+    const float m2 = __shfl_xor(st.m, off, 64), l2 = __shfl_xor(st.l, off, 64);
+    const float mn = fmaxf(st.m, m2);
+    const float ms = mn == -INFINITY ? 0.f : mn;
+    const float a1 = fexp2(st.m - ms), a2 = fexp2(m2 - ms);
+    st.l = st.l * a1 + l2 * a2;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) st.o[i] = st.o[i] * a1 + __shfl_xor(st.o[i], off, 64) * a2;
+    st.m = mn;
+  }
+  if (g == 0) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) sm_o[wave][c * 8 + i] = st.o[i];
+    if (c == 0) {
+      sm_ml[wave][0] = st.m;
+      sm_ml[wave][1] = st.l;
+    }
+  }
+  __syncthreads();
+  if (tid < D / 2) {  // wave 0 holds the new key, so the maximum is finite
+    float mx = sm_ml[0][0];
+#pragma unroll
+    for (int w = 1; w < AD_WAVES; ++w) mx = fmaxf(mx, sm_ml[w][0]);
+    float l = 0.f, o0 = 0.f, o1 = 0.f;
+#pragma unroll
+    for (int w = 0; w < AD_WAVES; ++w) {
+      const float a = fexp2(sm_ml[w][0] - mx);
+      l = fmaf(sm_ml[w][1], a, l);
+      o0 = fmaf(sm_o[w][2 * tid], a, o0);
+      o1 = fmaf(sm_o[w][2 * tid + 1], a, o1);
+    }
+    reinterpret_cast<uint32_t*>(orow)[tid] = pack_bf2(o0 / l, o1 / l);
+  }
+}
+
+bool launch_attn_decode(const uint16_t* qkv_new, int64_t qkv_stride, uint16_t* k_cache, uint16_t* v_cache,
+                        int64_t k_sb, int64_t k_sh, int64_t v_sb, int64_t v_sh, const int* lens, int B, int H,
+                        int Lmax, int D, uint16_t* out, hipStream_t s) {
+  if ((D != 64 && D != 128) || B <= 0 || H <= 0 || Lmax <= 0 || (int64_t)B * H > 0x7fffffffLL) return false;
+  if (!qkv_new || !k_cache || !v_cache || !lens || !out) return false;
+  // 16-byte rows: every row start is a multiple of 8 elements from a 16-byte aligned base
+  if (qkv_stride % 8 || k_sb % 8 || k_sh % 8 || v_sb % 8 || v_sh % 8) return false;
+  const dim3 grid((unsigned)(B * H)), block(64 * AD_WAVES);
+  if (D == 64)
+    hipLaunchKernelGGL(attn_decode_kernel<64>, grid, block, 0, s, qkv_new, qkv_stride, k_cache, v_cache, k_sb, k_sh,
+                       v_sb, v_sh, lens, H, Lmax, out);
+  else
+    hipLaunchKernelGGL(attn_decode_kernel<128>, grid, block, 0, s, qkv_new, qkv_stride, k_cache, v_cache, k_sb, k_sh,
+                       v_sb, v_sh, lens, H, Lmax, out);
+  return true;
+}
+
+}  // namespace dpa

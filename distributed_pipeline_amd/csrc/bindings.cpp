@@ -1141,6 +1141,43 @@ static std::vector<at::Tensor> reverse_step(const at::Tensor& like, int64_t N, i
   return {out, out16};
 }
 
+// One decode step's cache append + single-query attention (csrc/attn_decode.hip): qkv_new [B, 3 H D]
+// bf16, k_cache / v_cache [B, H, Lmax, D] bf16 (updated in place; batch and head strides free, so
+// views into a larger buffer work), lens [B] int32 -> out [B, H D] bf16, or None for a case the
+// kernel does not cover (dtype, D, CPU tensors, row layout): the caller's PyTorch path takes it.
+static c10::optional<at::Tensor> attn_decode(const at::Tensor& qkv_new, at::Tensor& k_cache, at::Tensor& v_cache,
+                                             const at::Tensor& lens, int64_t n_heads) {
+  TORCH_CHECK(qkv_new.dim() == 2 && k_cache.dim() == 4 && v_cache.dim() == 4 && lens.dim() == 1 && n_heads > 0,
+              "attn_decode: qkv_new [B, 3 H D], caches [B, H, Lmax, D], lens [B]");
+  const int64_t B = k_cache.size(0), H = k_cache.size(1), Lmax = k_cache.size(2), D = k_cache.size(3);
+  TORCH_CHECK(H == n_heads && v_cache.sizes() == k_cache.sizes() && qkv_new.size(0) == B &&
+                  qkv_new.size(1) == 3 * H * D && lens.size(0) == B,
+              "attn_decode: shapes of qkv_new, the caches, lens and n_heads do not agree");
+  TORCH_CHECK(lens.scalar_type() == at::kInt, "attn_decode: lens must be int32");
+  for (const at::Tensor* t : {&qkv_new, (const at::Tensor*)&k_cache, (const at::Tensor*)&v_cache, &lens})
+    if (!t->is_cuda() || t->device() != qkv_new.device()) return c10::nullopt;
+  if (qkv_new.scalar_type() != at::kBFloat16 || k_cache.scalar_type() != at::kBFloat16 ||
+      v_cache.scalar_type() != at::kBFloat16)
+    return c10::nullopt;
+  if ((D != 64 && D != 128) || B == 0 || Lmax == 0 || Lmax > 0x7fffffffLL || B * H > 0x7fffffffLL) return c10::nullopt;
+  auto rows_ok = [&](const at::Tensor& c) {  // packed rows of D; 16-byte row starts
+    return c.stride(3) == 1 && c.stride(2) == D && c.stride(0) % 8 == 0 && c.stride(1) % 8 == 0 &&
+           reinterpret_cast<uintptr_t>(c.data_ptr()) % 16 == 0;
+  };
+  if (!rows_ok(k_cache) || !rows_ok(v_cache) || !lens.is_contiguous()) return c10::nullopt;
+  if (qkv_new.stride(1) != 1 || qkv_new.stride(0) % 8 != 0 || reinterpret_cast<uintptr_t>(qkv_new.data_ptr()) % 16 != 0)
+    return c10::nullopt;
+  const c10::DeviceGuard guard(qkv_new.device());
+  at::Tensor out = at::empty({B, H * D}, qkv_new.options());
+  const bool ok = dpa::launch_attn_decode(
+      reinterpret_cast<const uint16_t*>(qkv_new.data_ptr()), qkv_new.stride(0),
+      reinterpret_cast<uint16_t*>(k_cache.data_ptr()), reinterpret_cast<uint16_t*>(v_cache.data_ptr()),
+      k_cache.stride(0), k_cache.stride(1), v_cache.stride(0), v_cache.stride(1), lens.data_ptr<int>(), (int)B, (int)H,
+      (int)Lmax, (int)D, reinterpret_cast<uint16_t*>(out.data_ptr()), cur_stream());
+  if (!ok) return c10::nullopt;
+  return out;
+}
+
 // Clipped n-gram match counts of every pair of a group's K sequences (csrc/ngram_match.hip):
 // tokens [G, K, L] int32 / int64, lens [G, K] int32 -> int32 [G, K, K, 4], or None for a shape the
 // kernel does not cover.
@@ -1448,6 +1485,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("s") = 0.0, py::arg("seed") = 0, py::arg("step") = 0, py::arg("row_base") = 0,
         py::arg("tau") = 0.0, py::arg("erf_tau") = 0.0, py::arg("want_bf16") = false,
         py::arg("pred_prev") = py::none(), py::arg("idx_prev") = py::none(), py::arg("a_prev") = 0.0);
+  m.def("attn_decode", &attn_decode,
+        "KV-cache append + single-query attention of one decode step (caches updated in place) -> out [B, H D] bf16 | None (case not covered)",
+        py::arg("qkv_new"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"), py::arg("n_heads"));
   m.def("ngram_matches", &ngram_matches,
         "clipped 1..4-gram match counts of every sequence pair of a group -> int32 [G, K, K, 4] | None (shape not covered)",
         py::arg("tokens"), py::arg("lens"));

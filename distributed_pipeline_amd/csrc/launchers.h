@@ -211,6 +211,17 @@ bool launch_reverse_step(const float* x, const uint16_t* pred, const int64_t* id
                          const uint16_t* pred_prev = nullptr, const int64_t* idx_prev = nullptr,
                          float a_prev = 0.f);
 
+// ---- attn_decode.hip: KV-cache append + single-query attention (GPT-2 generation) -------
+// Row b with 0 <= lens[b] < Lmax: cache[b, h, lens[b]] = the new k / v of qkv_new ([B][3][H][D] bf16,
+// rows qkv_stride elements apart), out[b, h] = softmax(q K^T / sqrt D) V over the keys 0 .. lens[b]
+// (bf16 [B][H][D]); any other lens[b]: nothing stored, out row zeros.  Cache rows of D elements at
+// base + b * sb + h * sh + key * D; rows at or beyond lens[b] + 1 are never read; lens is not
+// modified.  false, with no launch: D not in {64, 128}, a stride that is no multiple of 8 elements,
+// an empty shape or a null pointer.  Bases must be 16-byte aligned.
+bool launch_attn_decode(const uint16_t* qkv_new, int64_t qkv_stride, uint16_t* k_cache, uint16_t* v_cache,
+                        int64_t k_sb, int64_t k_sh, int64_t v_sb, int64_t v_sh, const int* lens, int B, int H,
+                        int Lmax, int D, uint16_t* out, hipStream_t s);
+
 // ---- ngram_match.hip: clipped n-gram match counts of sequence pairs (MBR, BLEU) --------
 // m[g][i][j][n-1] = sum over the distinct n-grams y of min(count_i(y), count_j(y)), n = 1..4, for the
 // K sequences tokens[g][k][0 .. lens[g][k]) of every group (ids there in [0, 2^31); lens clamped to

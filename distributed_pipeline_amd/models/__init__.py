@@ -3,7 +3,7 @@ import torch
 
 from .diffuseq import TransformerNetModel, count_params
 from .gaussian_diffusion import GaussianDiffusion, create_gaussian_diffusion, get_named_beta_schedule
-from .gpt2 import GPT2LMModel
+from .gpt2 import GPT2LMModel, KVCache
 from .mlp_diffusion import MLPDiffusionModel
 from .resample import create_named_schedule_sampler
 
@@ -43,6 +43,6 @@ def build_model(*, model="diffuseq", precision="bf16", vocab_size=30522, hidden_
     raise ValueError(f"unknown model {model!r}")
 
 
-__all__ = ["TransformerNetModel", "MLPDiffusionModel", "GPT2LMModel", "GaussianDiffusion",
+__all__ = ["TransformerNetModel", "MLPDiffusionModel", "GPT2LMModel", "KVCache", "GaussianDiffusion",
            "create_gaussian_diffusion", "get_named_beta_schedule", "create_named_schedule_sampler",
            "build_model", "count_params", "compute_dtype_for"]

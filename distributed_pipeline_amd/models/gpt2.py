@@ -55,6 +55,138 @@ class GPT2LMModel(nn.Module):
         tgt = labels[:, 1:].reshape(-1)
         return ops.linear_cross_entropy(x, self.wte.weight, None, tgt).view(B, L - 1)
 
+    # ---- generation: K/V cache, prefill, one-token decode steps (inference only) ----------
+
+    def init_cache(self, batch, max_len, device=None, dtype=None):
+        """An empty cache for ``batch`` rows of up to ``max_len`` tokens (prompt + continuation)."""
+        cfg = self.cfg
+        if not 1 <= max_len <= cfg["max_position_embeddings"]:
+            raise ValueError(f"max_len {max_len} outside 1 .. max_position_embeddings "
+                             f"{cfg['max_position_embeddings']}")
+        device = self.wte.weight.device if device is None else device
+        dtype = self.compute_dtype if dtype is None else dtype
+        return KVCache(len(self.h), batch, cfg["num_heads"], max_len, cfg["hidden_size"] // cfg["num_heads"],
+                       device, dtype)
+
+    def _blocks(self, x, a, attend):
+        """The block stack of ``hidden_states`` in eval mode with ``attend(i, qkv)`` as layer i's
+        attention over its packed projection -> ln_f of the last residual stream."""
+        lns = [blk.ln_1 for blk in self.h] + [self.ln_f]
+        for i, blk in enumerate(self.h):
+            h = blk.attn_proj(attend(i, blk.attn.qkv(a)))
+            x, a = ops.residual_layernorm(h, x, blk.ln_2.weight, blk.ln_2.bias, 0.0, blk.ln_2.eps, False)
+            x, a = ops.residual_layernorm(ops.mlp(a, blk.mlp_fc, blk.mlp_proj), x, lns[i + 1].weight,
+                                          lns[i + 1].bias, 0.0, lns[i + 1].eps, False)
+        return a
+
+    @torch.no_grad()
+    def prefill(self, input_ids, lens, cache):
+        """Right-padded prompts ``input_ids`` [B, Lp] of ``1 <= lens[b] <= Lp`` tokens: one causal
+        forward (what stands behind a row's prompt never reaches it), each layer's K and V of the
+        prompt positions copied into ``cache``, ``cache.lens = lens`` -> the logits [B, V] at each
+        row's last prompt position."""
+        dt = self.compute_dtype
+        B, Lp = input_ids.shape
+        if Lp > cache.max_len or B != cache.batch:
+            raise ValueError(f"prompts [{B}, {Lp}] do not fit a cache of {cache.batch} rows x {cache.max_len}")
+        lens = lens.to(device=input_ids.device, dtype=torch.int32)
+        L = Lp
+        if input_ids.is_cuda and dt == torch.bfloat16 and Lp % 64:
+            # ops.attention's kernels take L % 64 == 0: pad on the right, which causality hides
+            L = min(-(-Lp // 64) * 64, self.cfg["max_position_embeddings"])
+            input_ids = torch.nn.functional.pad(input_ids, (0, L - Lp))
+        heads, D = cache.heads, cache.head_dim
+        inside = (torch.arange(Lp, device=input_ids.device).view(1, Lp) < lens.view(B, 1)).view(B, 1, Lp, 1)
+
+        def attend(i, qkv):
+            kv = qkv.view(B, L, 3, heads, D)[:, :Lp].permute(2, 0, 3, 1, 4)  # [3, B, H, Lp, D]
+            for dst, src in ((cache.k[i], kv[1]), (cache.v[i], kv[2])):
+                dst[:, :, :Lp] = torch.where(inside, src.to(dst.dtype), dst[:, :, :Lp])
+            return ops.attention(qkv, heads, 0.0, True, False)
+
+        ln0 = self.h[0].ln_1
+        x, a = ops.residual_layernorm(self.wte(input_ids, dt), None, ln0.weight, ln0.bias, 0.0, ln0.eps, False,
+                                      pos=self.wpe(self.position_ids[:, :L], dt))
+        a = self._blocks(x, a, attend)
+        cache.lens = lens.clone()
+        last = a[torch.arange(B, device=a.device), (lens.long() - 1).clamp(0, Lp - 1)]
+        return ops.linear(last, self.wte.weight)
+
+    @torch.no_grad()
+    def decode_step(self, tokens, cache):
+        """One token per row at position ``cache.lens[b]`` -> the next-token logits [B, V];
+        ``cache.lens`` advances on the device.  A parked row (``lens`` outside 0 .. max_len - 1)
+        does no cache work, keeps its ``lens``, and its logits mean nothing."""
+        from ..ops.decode import attention_decode
+        dt = self.compute_dtype
+        B = tokens.shape[0]
+        heads = cache.heads
+        pos = cache.lens.long().clamp(0, self.cfg["max_position_embeddings"] - 1)
+        # the B rows stand where hidden_states has the L positions of one sequence, so the
+        # embedding sum and every LayerNorm run in the kernels (and roundings) of the full forward
+        ln0 = self.h[0].ln_1
+        x, a = ops.residual_layernorm(self.wte(tokens.view(1, B), dt), None, ln0.weight, ln0.bias, 0.0, ln0.eps,
+                                      False, pos=self.wpe(pos, dt))
+
+        def attend(i, qkv):
+            return attention_decode(qkv.view(B, -1), cache.k[i], cache.v[i], cache.lens, heads).view(1, B, -1)
+
+        a = self._blocks(x, a, attend)
+        cache.lens += ((cache.lens >= 0) & (cache.lens < cache.max_len)).to(cache.lens.dtype)
+        return ops.linear(a.view(B, -1), self.wte.weight)
+
+    @torch.no_grad()
+    def generate(self, input_ids, lens, max_new_tokens, *, temperature=1.0, top_k=0, top_p=0.0, eos_id=None,
+                 generator=None, cache=None, check_every=16):
+        """Continue right-padded prompts -> (tokens [B, max_new_tokens], new_lens [B]).
+
+        ``temperature == 0`` is greedy (ties to the lowest id); otherwise ``logits / temperature``,
+        ``top_k``, ``top_p``, one draw with ``generator`` (utils/lm_sampling.py).  A row stops when
+        it has emitted ``eos_id`` or its cache is full: it is parked (``cache.lens[b] = -1``, no
+        further cache work) and the rest of its output row is ``eos_id`` (0 without one).
+        ``new_lens[b]`` counts the tokens the row really produced, a closing ``eos_id`` included.
+        ``cache``: one from :meth:`init_cache` to use (default: a new one of just the size needed).
+        The loop runs on the device; the host looks at it once every ``check_every`` steps (0:
+        never), to stop early when every row has finished."""
+        from utils.lm_sampling import sample_next
+        B, Lp = input_ids.shape
+        dev = input_ids.device
+        if cache is None:
+            cache = self.init_cache(B, min(Lp + max_new_tokens, self.cfg["max_position_embeddings"]), dev)
+        fill = 0 if eos_id is None else int(eos_id)
+        out = torch.full((B, max_new_tokens), fill, dtype=torch.long, device=dev)
+        new_lens = torch.zeros(B, dtype=torch.long, device=dev)
+        done = torch.zeros(B, dtype=torch.bool, device=dev)
+        logits = self.prefill(input_ids, lens, cache)
+        for t in range(max_new_tokens):
+            tok = sample_next(logits, temperature, top_k, top_p, generator)
+            tok = torch.where(done, fill, tok)
+            out[:, t] = tok
+            new_lens += (~done).to(new_lens.dtype)
+            if eos_id is not None:
+                done = done | (tok == fill)
+            done = done | (cache.lens >= cache.max_len)  # no room to run this token
+            if t + 1 == max_new_tokens:
+                break
+            cache.lens.masked_fill_(done, -1)
+            if check_every and (t + 1) % check_every == 0 and bool(done.all()):
+                break
+            logits = self.decode_step(tok, cache)
+        cache.lens.masked_fill_(done, -1)
+        return out, new_lens
+
+
+class KVCache:
+    """Per-layer K / V of shape [B, H, max_len, D] - views into one buffer - and ``lens`` int32
+    [B], the tokens cached per row (outside 0 .. max_len - 1: a parked row)."""
+
+    def __init__(self, layers, batch, heads, max_len, head_dim, device, dtype):
+        self.batch, self.heads, self.max_len, self.head_dim = batch, heads, max_len, head_dim
+        self.buf = torch.zeros(layers, 2, batch, heads, max_len, head_dim, device=device, dtype=dtype)
+        self.k = [self.buf[i, 0] for i in range(layers)]
+        self.v = [self.buf[i, 1] for i in range(layers)]
+        self.lens = torch.zeros(batch, dtype=torch.int32, device=device)
+
 
 def _gpt2_train_flops_per_sample(self, seq_len):
     """6*P_lin + causal attention (~6*L*H per layer, half of the full 12*L*H) per

@@ -1,0 +1,87 @@
+"""
+Entry point: ``python -m run.generate --config_json cfg.json --model_path DIR --out_path out.jsonl``
+
+Continues prompts with a trained GPT-2 checkpoint (one process; one GPU, or the CPU): settings ->
+model -> state dict -> ``eval()`` -> for each batch of the split the first ``prompt_len`` tokens
+of every ``input_ids`` row are the prompt, and ``GPT2LMModel.generate`` adds up to
+``max_new_tokens`` tokens through its K/V cache (one prefill forward, then one single-token
+decode step per new token) -> one JSON line per row with ``prompt``, ``continuation`` (cut at the
+first ``eos_id``) and ``reference`` (the row's own next ``max_new_tokens`` tokens), as id lists.
+
+``--config_json`` takes the ``training_args.json`` of the training run as it is
+(config/generate.py).  ``--temperature 0`` is greedy and ignores the seed; otherwise
+``--temperature``, ``--top_k`` and ``--top_p`` shape the draw and ``--seed`` reproduces it.
+"""
+import json
+import os
+
+from config.generate import GenerateSettings
+from run.sample import find_checkpoint, shadow_frozen_weights
+
+
+def create_parser():
+    return GenerateSettings.to_argparse(add_json=True)
+
+
+def main(namespace):
+    args: GenerateSettings = GenerateSettings.from_argparse(namespace)
+    args.check()  # the model family and the sampling values, before any checkpoint is read
+
+    import torch
+
+    from basic_utils import dist_util
+    from data import load_data_from_args
+    from utils.initialization import create_model_from_config
+
+    dev = torch.device("cuda:0") if torch.cuda.is_available() else torch.device("cpu")
+    if dev.type == "cuda":
+        torch.cuda.set_device(dev)
+
+    model = create_model_from_config(**args.dict())
+    ckpt = find_checkpoint(args.model_path, args.use_ema)
+    print(f"### loading {ckpt}")
+    model.load_state_dict(dist_util.load_state_dict(ckpt, map_location="cpu"))
+    model.to(dev).eval()
+    if args.precision == "bf16":
+        shadow_frozen_weights(model)
+
+    # seed=0: ``--seed`` is the sampling seed alone; it must not also pick the prompts (the synthetic
+    # dataset draws its tokens from its seed), or a greedy run would depend on it
+    data = load_data_from_args(split=args.split, data_dir=args.data_dir, batch_size=args.batch_size,
+                               deterministic=True, loop=False, num_loader_proc=0,
+                               dataset=args.dataset, seq_len=args.seq_len, vocab_size=args.vocab_size,
+                               seed=0, model=args.model)
+    out_path = args.out_path
+    if not out_path:
+        stem = os.path.splitext(os.path.basename(ckpt))[0]
+        out_path = os.path.join(os.path.dirname(os.path.abspath(ckpt)), f"generated_{stem}_seed{args.seed}.jsonl")
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(args.seed)
+    eos = None if args.eos_id < 0 else args.eos_id
+    Lp, Ln = args.prompt_len, args.max_new_tokens
+    n = 0
+    with open(out_path, "w") as fout:
+        for b, batch in enumerate(data):
+            if b >= args.num_batches:
+                break
+            ids = batch["input_ids"].to(dev)
+            lens = torch.full((ids.shape[0],), Lp, dtype=torch.int32, device=dev)
+            toks, new_lens = model.generate(ids[:, :Lp].contiguous(), lens, Ln, temperature=args.temperature,
+                                            top_k=args.top_k, top_p=args.top_p, eos_id=eos, generator=gen)
+            ids, toks, new_lens = ids.cpu(), toks.cpu(), new_lens.cpu()
+            for i in range(ids.shape[0]):
+                cont = toks[i, :int(new_lens[i])].tolist()
+                if eos is not None and eos in cont:
+                    cont = cont[:cont.index(eos)]
+                line = {"prompt": ids[i, :Lp].tolist(), "continuation": cont,
+                        "reference": ids[i, Lp:Lp + Ln].tolist()}
+                fout.write(json.dumps(line) + "\n")
+            n += ids.shape[0]
+    print(f"### wrote {n} continuations to {out_path}")
+    return out_path
+
+
+if __name__ == "__main__":
+    main(create_parser().parse_args())

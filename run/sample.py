@@ -61,6 +61,14 @@ def find_checkpoint(model_path, use_ema=""):
     return os.path.join(model_path, best[1])
 
 
+def shadow_frozen_weights(model):
+    """Frozen weights: one bf16 cast per parameter, not one per forward (ops.shadow)."""
+    import torch
+
+    for p in model.parameters():
+        p._dpa_shadow = p.detach().to(torch.bfloat16)
+
+
 def load_vocab(data_dir):
     """id -> token of ``{data_dir}/vocab.txt`` (the WordPiece file the dataset's tokenizer reads),
     or None."""
@@ -140,8 +148,7 @@ def main(namespace):
     model.load_state_dict(dist_util.load_state_dict(ckpt, map_location="cpu"))
     model.to(dev).eval()
     if args.precision == "bf16":
-        for p in model.parameters():  # frozen weights: one bf16 cast, not one per forward (ops.shadow)
-            p._dpa_shadow = p.detach().to(torch.bfloat16)
+        shadow_frozen_weights(model)
 
     data = load_data_from_args(split=args.split, data_dir=args.data_dir, batch_size=args.batch_size,
                                deterministic=True, loop=False, num_loader_proc=0,
