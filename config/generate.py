@@ -40,6 +40,11 @@ class ContinueSettings(S):
         = _(-1, "Token id that ends a continuation; -1 = none.")
     seed: int \
         = _(102, "Sampling seed.")
+    noise: Choice("torch", "philox") \
+        = _("torch", "torch: one torch.Generator seeded with seed, consumed in batch order (a continuation "
+                     "depends on the batching). philox: counter-based noise keyed by (seed, step, sample index "
+                     "in the split, token id), so a row's draws do not depend on the batching; on a GPU the "
+                     "choice of the next token is then one fused kernel per step.")
     out_path: str \
         = _("", "Output .jsonl file (default: generated_<checkpoint>_seed<seed>.jsonl next to the checkpoint).")
     precision: Choice("bf16", "fp32") \
@@ -76,6 +81,8 @@ class GenerateSettings(
         """Reject what no checkpoint could make sense of (before one is read)."""
         if self.model != "gpt2":
             raise ValueError(f"run.generate continues prompts with the gpt2 model, not {self.model!r}")
+        if self.noise not in ("torch", "philox"):
+            raise ValueError(f"--noise must be torch or philox, got {self.noise!r}")
         if not 0.0 <= self.top_p <= 1.0:
             raise ValueError(f"--top_p must be in [0, 1], got {self.top_p}")
         if self.temperature < 0:

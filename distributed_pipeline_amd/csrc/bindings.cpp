@@ -1178,6 +1178,50 @@ static c10::optional<at::Tensor> attn_decode(const at::Tensor& qkv_new, at::Tens
   return out;
 }
 
+// One next-token draw per row of logits [B, V] (csrc/sample.hip; the definition is in ops/decode.py):
+// -> [tokens int64 [B]], with return_stats also thr fp32 [B] and kept int32 [B]; None for a case the
+// kernel does not cover (CPU tensor, dtype, V > 65536, a last stride other than 1, B == 0).  seed and
+// row_base carry 64 bits in their two's complement; step is used modulo 2^32.
+static c10::optional<std::vector<at::Tensor>> sample_tokens(const at::Tensor& logits, double temperature,
+                                                            int64_t top_k, double top_p, int64_t seed, int64_t step,
+                                                            int64_t row_base, bool return_stats) {
+  TORCH_CHECK(logits.dim() == 2, "sample_tokens: logits [B, V]");
+  TORCH_CHECK(temperature > 0, "sample_tokens: temperature must be > 0");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  if (!logits.is_cuda() || (logits.scalar_type() != at::kFloat && logits.scalar_type() != at::kBFloat16))
+    return c10::nullopt;
+  if (B < 1 || B > 0x7fffffffLL || V < 1 || V > 65536 || logits.stride(1) != 1 || logits.stride(0) < 0)
+    return c10::nullopt;
+  const c10::DeviceGuard guard(logits.device());
+  auto opt = at::TensorOptions().device(logits.device());
+  std::vector<at::Tensor> out{at::empty({B}, opt.dtype(at::kLong))};
+  if (return_stats) {
+    out.push_back(at::empty({B}, opt.dtype(at::kFloat)));
+    out.push_back(at::empty({B}, opt.dtype(at::kInt)));
+  }
+  const int k = (top_k > 0 && top_k < V) ? (int)top_k : 0;
+  const bool ok = dpa::launch_sample_tokens(
+      logits.data_ptr(), logits.scalar_type() == at::kBFloat16, logits.stride(0), B, (int)V, (float)temperature, k,
+      (float)top_p, (uint64_t)seed, (uint32_t)step, (uint64_t)row_base, out[0].data_ptr<int64_t>(),
+      return_stats ? out[1].data_ptr<float>() : nullptr, return_stats ? out[2].data_ptr<int>() : nullptr,
+      cur_stream());
+  if (!ok) return c10::nullopt;
+  return out;
+}
+
+// The uniforms sample_tokens draws with -> fp32 [B, V] on `like`'s device, or None (a CPU tensor, a
+// shape the kernel does not cover).
+static c10::optional<at::Tensor> sample_uniforms(const at::Tensor& like, int64_t seed, int64_t step,
+                                                 int64_t row_base, int64_t B, int64_t V) {
+  if (!like.is_cuda() || B < 1 || V < 1 || V > 65536 || B > 0x7fffffffLL) return c10::nullopt;
+  const c10::DeviceGuard guard(like.device());
+  at::Tensor out = at::empty({B, V}, at::TensorOptions().device(like.device()).dtype(at::kFloat));
+  if (!dpa::launch_sample_uniforms(out.data_ptr<float>(), B, (int)V, (uint64_t)seed, (uint32_t)step,
+                                   (uint64_t)row_base, cur_stream()))
+    return c10::nullopt;
+  return out;
+}
+
 // Clipped n-gram match counts of every pair of a group's K sequences (csrc/ngram_match.hip):
 // tokens [G, K, L] int32 / int64, lens [G, K] int32 -> int32 [G, K, K, 4], or None for a shape the
 // kernel does not cover.
@@ -1488,6 +1532,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_decode", &attn_decode,
         "KV-cache append + single-query attention of one decode step (caches updated in place) -> out [B, H D] bf16 | None (case not covered)",
         py::arg("qkv_new"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"), py::arg("n_heads"));
+  m.def("sample_tokens", &sample_tokens,
+        "temperature / top-k / top-p next-token draw with counter-based noise -> [tokens] or [tokens, thr, kept] | None (case not covered)",
+        py::arg("logits"), py::arg("temperature"), py::arg("top_k"), py::arg("top_p"), py::arg("seed"),
+        py::arg("step"), py::arg("row_base"), py::arg("return_stats") = false);
+  m.def("sample_uniforms", &sample_uniforms,
+        "the uniforms of sample_tokens -> fp32 [B, V] | None (case not covered)", py::arg("like"), py::arg("seed"),
+        py::arg("step"), py::arg("row_base"), py::arg("B"), py::arg("V"));
   m.def("ngram_matches", &ngram_matches,
         "clipped 1..4-gram match counts of every sequence pair of a group -> int32 [G, K, K, 4] | None (shape not covered)",
         py::arg("tokens"), py::arg("lens"));

@@ -222,6 +222,21 @@ bool launch_attn_decode(const uint16_t* qkv_new, int64_t qkv_stride, uint16_t* k
                         int64_t k_sb, int64_t k_sh, int64_t v_sb, int64_t v_sh, const int* lens, int B, int H,
                         int Lmax, int D, uint16_t* out, hipStream_t s);
 
+// ---- sample.hip: temperature / top-k / top-p next-token draw (GPT-2 generation) ---------
+// tokens[b] = the id drawn for row b of logits ([B][V] fp32 or bf16, rows row_stride elements apart, any
+// alignment): s = logit / temperature, top_k (0 < top_k < V, ties with the k-th kept), top_p (0 < top_p <
+// 1) on what is left, then Gumbel-max with Philox uniforms keyed by (seed, step) and counted by the global
+// group index (row_base + b) ceil(V / 4) + v / 4.  A row whose maximum is not finite gets the lowest id
+// holding it.  thr / kept (either may be null): the smallest kept s and the size of the kept set (the
+// maximum and 0 for such a row).  One launch, no workspace.  false, with no launch: V outside 1 .. 65536,
+// B outside 1 .. 2^31 - 1, temperature not > 0, or a null pointer.
+bool launch_sample_tokens(const void* logits, bool bf16, int64_t row_stride, int64_t B, int V, float temperature,
+                          int top_k, float top_p, uint64_t seed, uint32_t step, uint64_t row_base,
+                          int64_t* tokens, float* thr, int* kept, hipStream_t st);
+// out[b][v] = the uniform u_v in (0, 1) that launch_sample_tokens draws with (fp32 [B][V], contiguous).
+bool launch_sample_uniforms(float* out, int64_t B, int V, uint64_t seed, uint32_t step, uint64_t row_base,
+                            hipStream_t st);
+
 // ---- ngram_match.hip: clipped n-gram match counts of sequence pairs (MBR, BLEU) --------
 // m[g][i][j][n-1] = sum over the distinct n-grams y of min(count_i(y), count_j(y)), n = 1..4, for the
 // K sequences tokens[g][k][0 .. lens[g][k]) of every group (ids there in [0, 2^31); lens clamped to

@@ -137,11 +137,14 @@ class GPT2LMModel(nn.Module):
 
     @torch.no_grad()
     def generate(self, input_ids, lens, max_new_tokens, *, temperature=1.0, top_k=0, top_p=0.0, eos_id=None,
-                 generator=None, cache=None, check_every=16):
+                 generator=None, cache=None, check_every=16, noise_seed=None, row_base=0):
         """Continue right-padded prompts -> (tokens [B, max_new_tokens], new_lens [B]).
 
         ``temperature == 0`` is greedy (ties to the lowest id); otherwise ``logits / temperature``,
-        ``top_k``, ``top_p``, one draw with ``generator`` (utils/lm_sampling.py).  A row stops when
+        ``top_k``, ``top_p``, one draw with ``generator`` (utils/lm_sampling.py) - or, with an
+        integer ``noise_seed``, step t draws with ``ops.decode.sample_tokens(..., seed=noise_seed,
+        step=t, row_base=row_base)``: counter-based noise keyed by (seed, step, ``row_base`` + b, id),
+        the same for a row in whatever batch it stands, and ``generator`` is not touched.  A row stops when
         it has emitted ``eos_id`` or its cache is full: it is parked (``cache.lens[b] = -1``, no
         further cache work) and the rest of its output row is ``eos_id`` (0 without one).
         ``new_lens[b]`` counts the tokens the row really produced, a closing ``eos_id`` included.
@@ -149,6 +152,8 @@ class GPT2LMModel(nn.Module):
         The loop runs on the device; the host looks at it once every ``check_every`` steps (0:
         never), to stop early when every row has finished."""
         from utils.lm_sampling import sample_next
+        from ..ops.decode import sample_tokens
+        philox = noise_seed is not None and temperature > 0
         B, Lp = input_ids.shape
         dev = input_ids.device
         if cache is None:
@@ -159,7 +164,11 @@ class GPT2LMModel(nn.Module):
         done = torch.zeros(B, dtype=torch.bool, device=dev)
         logits = self.prefill(input_ids, lens, cache)
         for t in range(max_new_tokens):
-            tok = sample_next(logits, temperature, top_k, top_p, generator)
+            if philox:
+                tok = sample_tokens(logits, temperature=temperature, top_k=top_k, top_p=top_p, seed=int(noise_seed),
+                                    step=t, row_base=row_base)
+            else:
+                tok = sample_next(logits, temperature, top_k, top_p, generator)
             tok = torch.where(done, fill, tok)
             out[:, t] = tok
             new_lens += (~done).to(new_lens.dtype)

@@ -11,6 +11,8 @@ first ``eos_id``) and ``reference`` (the row's own next ``max_new_tokens`` token
 ``--config_json`` takes the ``training_args.json`` of the training run as it is
 (config/generate.py).  ``--temperature 0`` is greedy and ignores the seed; otherwise
 ``--temperature``, ``--top_k`` and ``--top_p`` shape the draw and ``--seed`` reproduces it.
+``--noise philox`` draws with ``ops.decode.sample_tokens``: noise keyed by (seed, step, the row's
+index in the split, token id), so a row's draws do not depend on ``--batch_size``.
 """
 import json
 import os
@@ -69,7 +71,8 @@ def main(namespace):
             ids = batch["input_ids"].to(dev)
             lens = torch.full((ids.shape[0],), Lp, dtype=torch.int32, device=dev)
             toks, new_lens = model.generate(ids[:, :Lp].contiguous(), lens, Ln, temperature=args.temperature,
-                                            top_k=args.top_k, top_p=args.top_p, eos_id=eos, generator=gen)
+                                            top_k=args.top_k, top_p=args.top_p, eos_id=eos, generator=gen,
+                                            noise_seed=args.seed if args.noise == "philox" else None, row_base=n)
             ids, toks, new_lens = ids.cpu(), toks.cpu(), new_lens.cpu()
             for i in range(ids.shape[0]):
                 cont = toks[i, :int(new_lens[i])].tolist()
