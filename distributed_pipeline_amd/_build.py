@@ -2,9 +2,10 @@
 In-tree build of the native extension ``distributed_pipeline_amd/_C*.so``.
 
 Compiles every ``csrc/*.hip`` kernel TU with ``hipcc --offload-arch=gfx950``
-(no torch headers -> seconds per file) and the single ``csrc/bindings.cpp``
-TU against the installed torch headers, then links one shared object next to
-this file so it travels with the repository snapshot to the GPU box.
+(no torch headers -> seconds per file) and the host TUs (``host_sources``: the
+module ``csrc/bindings.cpp``, a ``csrc/bind_<family>.cpp`` per kernel family,
+comm, runtime) against the installed torch headers, then links one shared object
+next to this file so it travels with the repository snapshot to the GPU box.
 
 No hipify step is involved: sources are written for HIP/CDNA4 directly.
 Object files are cached by content hash of (source, headers, flags), so a
@@ -26,6 +27,8 @@ CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(HERE, "build")
 ARCH = os.environ.get("DPA_OFFLOAD_ARCH", "gfx950")
 EXT_NAME = "_C"
+COMMON = ["-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-D__HIP_PLATFORM_AMD__=1",
+          "-Wno-unused-result", "-Wno-unused-command-line-argument"]  # every TU, before its -O flags
 
 
 def _hipcc():
@@ -68,26 +71,38 @@ def _run(cmd):
     return proc.stdout
 
 
+def host_sources(csrc):
+    """Host-side C++ TUs (torch / c10d APIs) of a csrc directory, compiled with ``bind_flags``."""
+    return [p for sub in ("", "comm", "runtime") for p in sorted(glob.glob(os.path.join(csrc, sub, "*.cpp")))]
+
+
+def bind_flags(ext_name, common):
+    """``common`` (COMMON + optimisation flags) plus what a host TU of the module ``ext_name`` needs.
+    Host TUs hold no kernels: no device pass over the torch headers (half of each one's compile time)."""
+    tinc, _, abi = _torch_paths()
+    return common + ["--offload-host-only", "-DUSE_ROCM=1", "-DTORCH_EXTENSION_NAME=" + ext_name,
+                     "-DTORCH_API_INCLUDE_EXTENSION_H", "-D_GLIBCXX_USE_CXX11_ABI=%d" % abi,
+                     "-I" + sysconfig.get_paths()["include"], "-Wno-deprecated-declarations"] + ["-I" + p for p in tinc]
+
+
+def link_libs(rccl=True):
+    tlib = _torch_paths()[1]  # rccl: torch's own librccl, one RCCL per process
+    return ["-L" + tlib, "-lc10", "-lc10_hip", "-ltorch", "-ltorch_cpu", "-ltorch_hip", "-ltorch_python",
+            "-Wl,-rpath," + tlib] + (["-lrccl"] if rccl else [])
+
+
 def build(force=False, jobs=None, debug=False, verbose=True):
     os.makedirs(BUILD, exist_ok=True)
     headers = glob.glob(os.path.join(CSRC, "*.h"))
     kernels = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
-    binding = os.path.join(CSRC, "bindings.cpp")
-    # host-side C++ (torch / c10d APIs): compiled with the binding flags
-    host_cpp = sorted(glob.glob(os.path.join(CSRC, "comm", "*.cpp")) + glob.glob(os.path.join(CSRC, "runtime", "*.cpp")))
-    opt = ["-O0", "-g"] if debug else ["-O3"]
-    common = ["-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-D__HIP_PLATFORM_AMD__=1",
-              "-Wno-unused-result", "-Wno-unused-command-line-argument"] + opt
-    tinc, tlib, abi = _torch_paths()
-    py_inc = sysconfig.get_paths()["include"]
-    bind_flags = common + ["-DUSE_ROCM=1", "-DTORCH_EXTENSION_NAME=" + EXT_NAME,
-                           "-DTORCH_API_INCLUDE_EXTENSION_H", "-D_GLIBCXX_USE_CXX11_ABI=%d" % abi,
-                           "-I" + py_inc, "-Wno-deprecated-declarations"] + ["-I" + p for p in tinc]
+    host = host_sources(CSRC)
+    common = COMMON + (["-O0", "-g"] if debug else ["-O3"])
+    bind = bind_flags(EXT_NAME, common)
 
     jobs_todo = []
     objects = []
-    for src in kernels + [binding] + host_cpp:
-        flags = bind_flags if (src == binding or src in host_cpp) else common
+    for src in kernels + host:
+        flags = bind if src in host else common
         key = _hash_files([src] + headers, " ".join(flags))
         obj = os.path.join(BUILD, os.path.basename(src) + "." + key + ".o")
         objects.append(obj)
@@ -109,10 +124,7 @@ def build(force=False, jobs=None, debug=False, verbose=True):
     up_to_date = (os.path.exists(target) and os.path.exists(stamp)
                   and open(stamp).read().strip() == link_key)
     if force or not up_to_date:
-        cmd = [_hipcc(), "-shared", "-fPIC", "--offload-arch=" + ARCH, "-o", target] + objects + [
-            "-L" + tlib, "-lc10", "-lc10_hip", "-ltorch", "-ltorch_cpu", "-ltorch_hip",
-            "-ltorch_python", "-lrccl", "-Wl,-rpath," + tlib]  # torch's own librccl: one RCCL per process
-        _run(cmd)
+        _run([_hipcc(), "-shared", "-fPIC", "--offload-arch=" + ARCH, "-o", target] + objects + link_libs())
         with open(stamp, "w") as f:
             f.write(link_key)
         if verbose:

@@ -1,0 +1,116 @@
+// Bindings of the generation and text-metric kernels: token sampling (sample.hip) and the
+// per-group n-gram / LCS counts (ngram_match.hip, ngram_distinct.hip, lcs.hip).
+#include "bind_util.h"
+
+// One next-token draw per row of logits [B, V] (csrc/sample.hip; the definition is in ops/decode.py):
+// -> [tokens int64 [B]], with return_stats also thr fp32 [B] and kept int32 [B]; None for a case the
+// kernel does not cover (CPU tensor, dtype, V > 65536, a last stride other than 1, B == 0).  seed and
+// row_base carry 64 bits in their two's complement; step is used modulo 2^32.
+static c10::optional<std::vector<at::Tensor>> sample_tokens(const at::Tensor& logits, double temperature,
+                                                            int64_t top_k, double top_p, int64_t seed, int64_t step,
+                                                            int64_t row_base, bool return_stats) {
+  TORCH_CHECK(logits.dim() == 2, "sample_tokens: logits [B, V]");
+  TORCH_CHECK(temperature > 0, "sample_tokens: temperature must be > 0");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  if (!logits.is_cuda() || (logits.scalar_type() != at::kFloat && logits.scalar_type() != at::kBFloat16))
+    return c10::nullopt;
+  if (B < 1 || B > 0x7fffffffLL || V < 1 || V > 65536 || logits.stride(1) != 1 || logits.stride(0) < 0)
+    return c10::nullopt;
+  const c10::DeviceGuard guard(logits.device());
+  auto opt = at::TensorOptions().device(logits.device());
+  std::vector<at::Tensor> out{at::empty({B}, opt.dtype(at::kLong))};
+  if (return_stats) {
+    out.push_back(at::empty({B}, opt.dtype(at::kFloat)));
+    out.push_back(at::empty({B}, opt.dtype(at::kInt)));
+  }
+  const int k = (top_k > 0 && top_k < V) ? (int)top_k : 0;
+  const bool ok = dpa::launch_sample_tokens(
+      logits.data_ptr(), logits.scalar_type() == at::kBFloat16, logits.stride(0), B, (int)V, (float)temperature, k,
+      (float)top_p, (uint64_t)seed, (uint32_t)step, (uint64_t)row_base, out[0].data_ptr<int64_t>(),
+      return_stats ? out[1].data_ptr<float>() : nullptr, return_stats ? out[2].data_ptr<int>() : nullptr,
+      cur_stream());
+  if (!ok) return c10::nullopt;
+  return out;
+}
+
+// The uniforms sample_tokens draws with -> fp32 [B, V] on `like`'s device, or None (a CPU tensor, a
+// shape the kernel does not cover).
+static c10::optional<at::Tensor> sample_uniforms(const at::Tensor& like, int64_t seed, int64_t step,
+                                                 int64_t row_base, int64_t B, int64_t V) {
+  if (!like.is_cuda() || B < 1 || V < 1 || V > 65536 || B > 0x7fffffffLL) return c10::nullopt;
+  const c10::DeviceGuard guard(like.device());
+  at::Tensor out = at::empty({B, V}, at::TensorOptions().device(like.device()).dtype(at::kFloat));
+  if (!dpa::launch_sample_uniforms(out.data_ptr<float>(), B, (int)V, (uint64_t)seed, (uint32_t)step,
+                                   (uint64_t)row_base, cur_stream()))
+    return c10::nullopt;
+  return out;
+}
+
+// ---- per-group token ops: tokens [G, K, L] int32 / int64, lens [G, K] int32 -> int32 counts ----
+static void check_token_group(const at::Tensor& tokens, const at::Tensor& lens, const char* op) {
+  CHECK_DEV(tokens); CHECK_CONTIG(tokens); CHECK_DEV(lens); CHECK_CONTIG(lens);
+  TORCH_CHECK(tokens.scalar_type() == at::kInt || tokens.scalar_type() == at::kLong, op,
+              ": tokens must be int32 or int64");
+  TORCH_CHECK(lens.scalar_type() == at::kInt, op, ": lens must be int32");
+  TORCH_CHECK(tokens.dim() == 3 && lens.dim() == 2 && lens.size(0) == tokens.size(0) &&
+                  lens.size(1) == tokens.size(1) && lens.device() == tokens.device(),
+              op, ": tokens [G, K, L], lens [G, K] on one device");
+}
+
+using TokenGroupLauncher = bool (*)(const void*, bool, const int*, int64_t, int, int, int*, hipStream_t);
+
+// the int32 result of `shape` from checked inputs, or None for a shape the kernel does not cover
+static c10::optional<at::Tensor> run_token_group(const at::Tensor& tokens, const at::Tensor& lens,
+                                                 at::IntArrayRef shape, TokenGroupLauncher launch) {
+  const int64_t G = tokens.size(0), K = tokens.size(1), L = tokens.size(2);
+  const c10::DeviceGuard guard(tokens.device());
+  at::Tensor out = at::empty(shape, tokens.options().dtype(at::kInt));
+  if (G == 0) return out;
+  if (K > 0x7fffffffLL || L > 0x7fffffffLL) return c10::nullopt;
+  if (!launch(tokens.data_ptr(), tokens.scalar_type() == at::kLong, lens.data_ptr<int>(), G, (int)K, (int)L,
+              out.data_ptr<int>(), cur_stream()))
+    return c10::nullopt;
+  return out;
+}
+
+// Clipped n-gram match counts of every pair of a group's K sequences (csrc/ngram_match.hip):
+// -> int32 [G, K, K, 4]
+static c10::optional<at::Tensor> ngram_matches(const at::Tensor& tokens, const at::Tensor& lens) {
+  check_token_group(tokens, lens, "ngram_matches");
+  const int64_t G = tokens.size(0), K = tokens.size(1);
+  return run_token_group(tokens, lens, {G, K, K, 4}, dpa::launch_ngram_match);
+}
+
+// Distinct n-gram counts of a group's K sequences and of their union (csrc/ngram_distinct.hip):
+// -> int32 [G, K + 1, 4]
+static c10::optional<at::Tensor> ngram_distinct(const at::Tensor& tokens, const at::Tensor& lens) {
+  check_token_group(tokens, lens, "ngram_distinct");
+  const int64_t G = tokens.size(0), K = tokens.size(1);
+  return run_token_group(tokens, lens, {G, K + 1, 4}, dpa::launch_ngram_distinct);
+}
+
+// LCS length of every pair of a group's K sequences (csrc/lcs.hip): -> int32 [G, K, K]
+static c10::optional<at::Tensor> lcs_lengths(const at::Tensor& tokens, const at::Tensor& lens) {
+  check_token_group(tokens, lens, "lcs_lengths");
+  const int64_t G = tokens.size(0), K = tokens.size(1);
+  return run_token_group(tokens, lens, {G, K, K}, dpa::launch_lcs_lengths);
+}
+
+void dpa::register_text(pybind11::module& m) {
+  m.def("sample_tokens", &sample_tokens,
+        "temperature / top-k / top-p next-token draw with counter-based noise -> [tokens] or [tokens, thr, kept] | None (case not covered)",
+        py::arg("logits"), py::arg("temperature"), py::arg("top_k"), py::arg("top_p"), py::arg("seed"),
+        py::arg("step"), py::arg("row_base"), py::arg("return_stats") = false);
+  m.def("sample_uniforms", &sample_uniforms,
+        "the uniforms of sample_tokens -> fp32 [B, V] | None (case not covered)", py::arg("like"), py::arg("seed"),
+        py::arg("step"), py::arg("row_base"), py::arg("B"), py::arg("V"));
+  m.def("ngram_matches", &ngram_matches,
+        "clipped 1..4-gram match counts of every sequence pair of a group -> int32 [G, K, K, 4] | None (shape not covered)",
+        py::arg("tokens"), py::arg("lens"));
+  m.def("ngram_distinct", &ngram_distinct,
+        "distinct 1..4-gram counts of every sequence of a group and of their union -> int32 [G, K + 1, 4] | None (shape not covered)",
+        py::arg("tokens"), py::arg("lens"));
+  m.def("lcs_lengths", &lcs_lengths,
+        "longest-common-subsequence length of every sequence pair of a group -> int32 [G, K, K] | None (shape not covered)",
+        py::arg("tokens"), py::arg("lens"));
+}

@@ -42,7 +42,7 @@ __device__ __forceinline__ bf16_t f2bf(float f) {
 // is 0 in eager runs.  A replayed HIP graph bakes its launches' offsets, so the trainer bumps
 // the base once per replay (rng_base_add, a one-thread kernel) and every replay draws fresh
 // numbers.  Internal linkage: one copy per translation unit, so each TU that draws numbers
-// exports its own rng_base_add_<tu> (DPA_RNG_BASE_EXPORT) and bindings.cpp bumps them all.
+// exports its own rng_base_add_<tu> (DPA_RNG_BASE_EXPORT) and bind_diffusion.cpp bumps them all.
 static __device__ uint32_t g_rng_base;
 static __global__ void rng_base_add_kernel(uint32_t d) {
   if (threadIdx.x == 0) g_rng_base += d;

@@ -1,6 +1,6 @@
 // Host-side launch entry points of the gfx950 kernels.  Kernels live in the
 // .hip translation units (which include no torch headers, so they compile in
-// seconds); bindings.cpp is the only TU that sees ATen.
+// seconds); only the binding TUs (bindings.cpp, bind_*.cpp, through bind_util.h) see ATen.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -443,7 +443,7 @@ __global__ void __launch_bounds__(256) lxent_fwd_dx_combine_kernel(
 // ---------------------------------------------------------------------------
 // ONEHOT: subtract the target's one-hot inside the kernel (a compare, subtract and select per
 // logit); false: the caller adds dW[target] -= g x and db[target] -= g as a sorted scatter
-// (bindings.cpp lxent_bwd), which leaves the per-logit work at exp, scale and column sum.
+// (bind_heads.cpp lxent_bwd), which leaves the per-logit work at exp, scale and column sum.
 template <int E, bool ONEHOT = true>
 __global__ void __launch_bounds__(512) lxent_dw_kernel(
     const bf16_t* __restrict__ x, const bf16_t* __restrict__ W, const bf16_t* __restrict__ bias,

@@ -11,6 +11,7 @@ kernels back to back.
 """
 import glob
 import os
+import shutil
 import subprocess
 import sys
 
@@ -27,8 +28,7 @@ def main(argv):
     csrc = B.CSRC
     if not files:  # the whole native tree of REV
         csrc = os.path.join(work, "csrc")
-        os.makedirs(os.path.join(csrc, "comm"), exist_ok=True)
-        os.makedirs(os.path.join(csrc, "runtime"), exist_ok=True)
+        shutil.rmtree(csrc, ignore_errors=True)  # the sources are globbed: none left over from another REV
         names = subprocess.check_output(["git", "-C", HERE, "ls-tree", "-r", "--name-only", rev,
                                          "distributed_pipeline_amd/csrc"], text=True).split()
         for n in names:
@@ -36,13 +36,8 @@ def main(argv):
             os.makedirs(os.path.dirname(dst), exist_ok=True)
             with open(dst, "w") as fh:
                 fh.write(subprocess.check_output(["git", "-C", HERE, "show", f"{rev}:{n}"], text=True))
-    tinc, tlib, abi = B._torch_paths()
-    import sysconfig
-    common = ["-std=c++17", "-fPIC", "--offload-arch=" + B.ARCH, "-D__HIP_PLATFORM_AMD__=1",
-              "-Wno-unused-result", "-Wno-unused-command-line-argument", "-O3", "-I" + csrc]
-    bind = common + ["-DUSE_ROCM=1", "-DTORCH_EXTENSION_NAME=_C_ab", "-DTORCH_API_INCLUDE_EXTENSION_H",
-                     "-D_GLIBCXX_USE_CXX11_ABI=%d" % abi, "-I" + sysconfig.get_paths()["include"],
-                     "-Wno-deprecated-declarations"] + ["-I" + p for p in tinc]
+    common = B.COMMON + ["-O3", "-I" + csrc]
+    bind = B.bind_flags("_C_ab", common)
     swapped = {os.path.basename(f) for f in files}
     objs = []
     for f in files:
@@ -59,15 +54,12 @@ def main(argv):
         obj = os.path.join(work, os.path.basename(src) + ".cur.o")
         B._run([B._hipcc()] + common + ["-c", src, "-o", obj])
         objs.append(obj)
-    for src in [os.path.join(csrc, "bindings.cpp")] + sorted(glob.glob(os.path.join(csrc, "comm", "*.cpp"))
-                                                          + glob.glob(os.path.join(csrc, "runtime", "*.cpp"))):
+    for src in B.host_sources(csrc):
         obj = os.path.join(work, os.path.basename(src) + ".ab.o")
         B._run([B._hipcc()] + bind + ["-c", src, "-o", obj])
         objs.append(obj)
     target = os.path.join(HERE, "distributed_pipeline_amd", "_C_ab" + B._ext_suffix())
-    B._run([B._hipcc(), "-shared", "-fPIC", "--offload-arch=" + B.ARCH, "-o", target] + objs + [
-        "-L" + tlib, "-lc10", "-lc10_hip", "-ltorch", "-ltorch_cpu", "-ltorch_hip", "-ltorch_python", "-lrccl",
-        "-Wl,-rpath," + tlib])
+    B._run([B._hipcc(), "-shared", "-fPIC", "--offload-arch=" + B.ARCH, "-o", target] + objs + B.link_libs())
     print(target)
 
 

@@ -29,15 +29,10 @@ def build():
     out_dir = os.path.join(B.HERE, "build_asan")
     os.makedirs(out_dir, exist_ok=True)
     name = "_C_asan"
-    tinc, tlib, abi = B._torch_paths()
-    import sysconfig
-    common = ["-std=c++17", "-fPIC", "--offload-arch=" + B.ARCH, "-O1", "-g",
-              "-Wno-unused-result", "-Wno-unused-command-line-argument"] + HOST_SAN
-    bind = common + ["-DUSE_ROCM=1", "-DTORCH_EXTENSION_NAME=" + name, "-DTORCH_API_INCLUDE_EXTENSION_H",
-                     "-D_GLIBCXX_USE_CXX11_ABI=%d" % abi, "-I" + sysconfig.get_paths()["include"],
-                     "-Wno-deprecated-declarations"] + ["-I" + p for p in tinc]
+    common = B.COMMON + ["-O1", "-g"] + HOST_SAN
+    bind = B.bind_flags(name, common)
     srcs = sorted(glob.glob(os.path.join(B.CSRC, "*.hip")))
-    host = [os.path.join(B.CSRC, "bindings.cpp")] + sorted(glob.glob(os.path.join(B.CSRC, "comm", "*.cpp")))
+    host = B.host_sources(B.CSRC)
     import concurrent.futures as cf
     jobs, objs = [], []
     for src in srcs + host:
@@ -49,9 +44,7 @@ def build():
         list(ex.map(B._run, jobs))
     target = os.path.join(B.HERE, name + B._ext_suffix())
     B._run([B._hipcc(), "-shared", "-fPIC", "--offload-arch=" + B.ARCH, "-fsanitize=address,undefined",
-            "-fno-gpu-sanitize", "-shared-libsan", "-o", target] + objs +
-           ["-L" + tlib, "-lc10", "-lc10_hip", "-ltorch", "-ltorch_cpu", "-ltorch_hip", "-ltorch_python",
-            "-Wl,-rpath," + tlib])
+            "-fno-gpu-sanitize", "-shared-libsan", "-o", target] + objs + B.link_libs(rccl=False))
     print(target)
     return target
 
