@@ -7,8 +7,11 @@
 static void sqnorm(const at::Tensor& g, at::Tensor& partial, at::Tensor& out, double scale,
                    double max_norm) {
   CHECK_DEV(g); CHECK_CONTIG(g); CHECK_ALIGNED(g);
-  CHECK_F32(partial); CHECK_F32(out);
+  CHECK_DEV(partial); CHECK_F32(partial); CHECK_CONTIG(partial);
+  CHECK_DEV(out); CHECK_F32(out); CHECK_CONTIG(out);
   TORCH_CHECK(g.numel() % 4 == 0, "flat grad buffer must be padded to a multiple of 4");
+  // the grid is capped at partial.numel() blocks: an empty one would be a 0-block launch
+  TORCH_CHECK(partial.numel() >= 1, "partial needs at least 1 float");
   TORCH_CHECK(out.numel() >= 3, "out needs 3 floats");
   const bool bf = g.scalar_type() == at::kBFloat16;
   TORCH_CHECK(bf || g.scalar_type() == at::kFloat, "grad must be fp32 or bf16");
@@ -24,6 +27,7 @@ static void adamw_ema(at::Tensor& p, const at::Tensor& g, at::Tensor& m, at::Ten
                       c10::optional<at::Tensor> skip) {
   for (auto* t : {&p, &m, &v}) { CHECK_DEV((*t)); CHECK_CONTIG((*t)); CHECK_F32((*t)); CHECK_ALIGNED((*t)); }
   CHECK_DEV(g); CHECK_CONTIG(g); CHECK_ALIGNED(g);
+  TORCH_CHECK(g.device() == p.device(), "g must be on the device of p");
   const int64_t n = p.numel();
   TORCH_CHECK(n % 4 == 0, "flat buffers must be padded to a multiple of 4");
   TORCH_CHECK(g.numel() == n && m.numel() == n && v.numel() == n, "size mismatch");
@@ -33,20 +37,25 @@ static void adamw_ema(at::Tensor& p, const at::Tensor& g, at::Tensor& m, at::Ten
   std::vector<float*> bufs;
   std::vector<float> r;
   for (size_t i = 0; i < emas.size(); ++i) {
-    CHECK_F32(emas[i]); CHECK_CONTIG(emas[i]); CHECK_ALIGNED(emas[i]);
+    CHECK_DEV(emas[i]); CHECK_F32(emas[i]); CHECK_CONTIG(emas[i]); CHECK_ALIGNED(emas[i]);
     TORCH_CHECK(emas[i].numel() == n, "ema size mismatch");
     bufs.push_back(emas[i].data_ptr<float>());
     r.push_back((float)rates[i]);
   }
   uint16_t* p16p = nullptr;
   if (has(p16)) {
-    CHECK_BF16((*p16)); CHECK_CONTIG((*p16));
+    CHECK_DEV((*p16)); CHECK_BF16((*p16)); CHECK_CONTIG((*p16));
     TORCH_CHECK(p16->numel() == n, "bf16 shadow size mismatch");
     TORCH_CHECK(reinterpret_cast<uintptr_t>(p16->data_ptr()) % 8 == 0, "bf16 shadow must be 8B aligned");
     p16p = bf_mut(*p16);
   }
   const float* clipp = nullptr;
-  if (has(clip)) { CHECK_F32((*clip)); clipp = clip->data_ptr<float>(); }
+  if (has(clip)) {
+    // [norm, coef, norm * coef] of sqnorm: the kernel reads clip[1]
+    CHECK_DEV((*clip)); CHECK_F32((*clip)); CHECK_CONTIG((*clip));
+    TORCH_CHECK(clip->numel() >= 2, "clip needs at least 2 floats");
+    clipp = clip->data_ptr<float>();
+  }
   const int* skipp = nullptr;
   if (has(skip)) {
     CHECK_DEV((*skip));
@@ -56,11 +65,12 @@ static void adamw_ema(at::Tensor& p, const at::Tensor& g, at::Tensor& m, at::Ten
   const c10::DeviceGuard guard(p.device());
   dpa::launch_adamw_ema(p.data_ptr<float>(), g.data_ptr(), bf, m.data_ptr<float>(),
                         v.data_ptr<float>(), p16p, bufs.data(), r.data(), (int)bufs.size(), n,
-                        (float)lr, (float)beta1, (float)beta2, (float)eps, (float)wd, step,
+                        (float)lr, beta1, beta2, (float)eps, (float)wd, step,
                         (float)grad_scale, clipp, cur_stream(), skipp);
 }
 
 static void ema_update(at::Tensor& e, const at::Tensor& p, double rate) {
+  CHECK_DEV(e); CHECK_DEV(p); CHECK_CONTIG(e); CHECK_CONTIG(p);
   CHECK_F32(e); CHECK_F32(p); CHECK_ALIGNED(e); CHECK_ALIGNED(p);
   TORCH_CHECK(e.numel() == p.numel() && e.numel() % 4 == 0, "ema size");
   const c10::DeviceGuard guard(p.device());
@@ -68,8 +78,10 @@ static void ema_update(at::Tensor& e, const at::Tensor& p, double rate) {
 }
 
 static void cast_bf16(const at::Tensor& src, at::Tensor& dst) {
+  CHECK_DEV(src); CHECK_DEV(dst); CHECK_CONTIG(src); CHECK_CONTIG(dst);
   CHECK_F32(src); CHECK_BF16(dst); CHECK_ALIGNED(src);
   TORCH_CHECK(src.numel() == dst.numel() && src.numel() % 4 == 0, "cast size");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(dst.data_ptr()) % 8 == 0, "dst must be 8B aligned");
   const c10::DeviceGuard guard(src.device());
   dpa::launch_cast_bf16(src.data_ptr<float>(), bf_mut(dst), src.numel(), cur_stream());
 }

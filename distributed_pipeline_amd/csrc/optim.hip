@@ -92,9 +92,11 @@ struct EmaArgs {
 template <typename T>
 __global__ void __launch_bounds__(256) adamw_ema_kernel(
     float* __restrict__ p, const T* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-    bf16_t* __restrict__ p16, EmaArgs ema, int64_t n, float lr, float beta1, float beta2,
-    float eps, float wd, float step_size, float inv_bc2_sqrt, float grad_scale,
-    const float* __restrict__ clip, const int* __restrict__ skip) {
+    bf16_t* __restrict__ p16, EmaArgs ema, int64_t n, float lr, float omb1, float beta2,
+    float omb2, float eps, float wd, float step_size, float inv_bc2_sqrt,
+    float grad_scale, const float* __restrict__ clip, const int* __restrict__ skip) {
+  // omb1 / omb2: 1 - beta rounded from double by the host.  1.f - beta2 here would be
+  // 1 - fp32(0.999) = 0.99998713e-3, 1.3e-5 off in every term of v.
   // skip != nullptr: the step is refused while *skip != 0 (a failed gradient
   // all-reduce, csrc/ipc_allreduce.hip) - parameters, moments and EMAs stay as they were
   if (skip && __builtin_nontemporal_load(skip) != 0) return;
@@ -110,8 +112,8 @@ __global__ void __launch_bounds__(256) adamw_ema_kernel(
     for (int k = 0; k < 4; ++k) {
       float gk = gv[k] * gs;
       float pk = pv[k] * decay;
-      float mk = mv[k] + (1.f - beta1) * (gk - mv[k]);
-      float vk = vv[k] * beta2 + (1.f - beta2) * gk * gk;
+      float mk = mv[k] + omb1 * (gk - mv[k]);
+      float vk = vv[k] * beta2 + omb2 * gk * gk;
       float denom = sqrtf(vk) * inv_bc2_sqrt + eps;
       pk = pk - step_size * (mk / denom);
       pv[k] = pk; mv[k] = mk; vv[k] = vk;
@@ -138,9 +140,12 @@ __global__ void __launch_bounds__(256) adamw_ema_kernel(
   }
 }
 
-// Plain EMA update (used when the optimizer is not the fused one).
+// Plain EMA update (used when the optimizer is not the fused one, and for the EMAs past the
+// fourth of adamw_ema, which pass its `skip` flag: nullptr, or the update is refused while
+// *skip != 0).
 __global__ void __launch_bounds__(256) ema_kernel(float* __restrict__ e, const float* __restrict__ p,
-                                                 int64_t n, float rate) {
+                                                 int64_t n, float rate, const int* __restrict__ skip) {
+  if (skip && __builtin_nontemporal_load(skip) != 0) return;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x * 4;
   for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
     f32x4 ev = *reinterpret_cast<f32x4*>(e + i);
@@ -200,7 +205,7 @@ void launch_sqnorm(const void* g, bool g_bf16, int64_t n, float* partial, int np
 
 void launch_adamw_ema(float* p, const void* g, bool g_bf16, float* m, float* v, uint16_t* p16,
                       float* const* ema_bufs, const float* ema_rates, int n_ema, int64_t n, float lr,
-                      float beta1, float beta2, float eps, float wd, int64_t step, float grad_scale,
+                      double beta1, double beta2, float eps, float wd, int64_t step, float grad_scale,
                       const float* clip, hipStream_t s, const int* skip) {
   EmaArgs ea;
   ea.count = n_ema > 4 ? 4 : n_ema;
@@ -208,28 +213,30 @@ void launch_adamw_ema(float* p, const void* g, bool g_bf16, float* m, float* v, 
     ea.buf[e] = e < ea.count ? ema_bufs[e] : nullptr;
     ea.rate[e] = e < ea.count ? ema_rates[e] : 0.f;
   }
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2 = 1.0 - pow(beta2, (double)step);
+  const float omb1 = (float)(1.0 - beta1), b2 = (float)beta2, omb2 = (float)(1.0 - beta2);
   const float step_size = (float)(lr / bc1);
   const float inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
   // ~1 MiB of work per block keeps ~8 blocks/CU resident on 256 CUs.
   int grid = grid_for(n, 4, 256, 256 * 8);
   if (g_bf16)
     hipLaunchKernelGGL(adamw_ema_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, p, (const bf16_t*)g,
-                       m, v, (bf16_t*)p16, ea, n, lr, beta1, beta2, eps, wd, step_size,
+                       m, v, (bf16_t*)p16, ea, n, lr, omb1, b2, omb2, eps, wd, step_size,
                        inv_bc2_sqrt, grad_scale, clip, skip);
   else
     hipLaunchKernelGGL(adamw_ema_kernel<float>, dim3(grid), dim3(256), 0, s, p, (const float*)g, m,
-                       v, (bf16_t*)p16, ea, n, lr, beta1, beta2, eps, wd, step_size, inv_bc2_sqrt,
+                       v, (bf16_t*)p16, ea, n, lr, omb1, b2, omb2, eps, wd, step_size, inv_bc2_sqrt,
                        grad_scale, clip, skip);
-  // More than 4 EMA rates: remaining ones as plain passes (not gated by `skip`: the
-  // engine raises on a set flag before the next step anyway).
+  // More than 4 EMA rates: remaining ones as plain passes, gated by the same `skip` flag, so a
+  // refused step leaves every EMA as it was.
   for (int e = 4; e < n_ema; ++e)
-    hipLaunchKernelGGL(ema_kernel, dim3(grid), dim3(256), 0, s, ema_bufs[e], p, n, ema_rates[e]);
+    hipLaunchKernelGGL(ema_kernel, dim3(grid), dim3(256), 0, s, ema_bufs[e], p, n, ema_rates[e], skip);
 }
 
 void launch_ema(float* e, const float* p, int64_t n, float rate, hipStream_t s) {
-  hipLaunchKernelGGL(ema_kernel, dim3(grid_for(n, 4, 256, 2048)), dim3(256), 0, s, e, p, n, rate);
+  hipLaunchKernelGGL(ema_kernel, dim3(grid_for(n, 4, 256, 2048)), dim3(256), 0, s, e, p, n, rate,
+                     (const int*)nullptr);
 }
 
 void launch_cast_f32(const uint16_t* src, float* dst, int64_t n, hipStream_t s) {

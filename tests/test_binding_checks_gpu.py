@@ -60,9 +60,46 @@ def _token_group_cases():
     return cases
 
 
-def _adamw(n=8, emas=1, rates=1, skip=None):
-    return ((f32(n), f32(n), f32(n), f32(n), None, [f32(n) for _ in range(emas)], [0.999] * rates,
-             1e-3, 0.9, 0.999, 1e-8, 0.0, 1, 1.0, None, skip), {})
+def _adamw(n=8, emas=1, rates=1, skip=None, clip=None, shadow=None, ema_list=None):
+    ema_list = [f32(n) for _ in range(emas)] if ema_list is None else ema_list
+    return ((f32(n), f32(n), f32(n), f32(n), shadow, ema_list, [0.999] * rates,
+             1e-3, 0.9, 0.999, 1e-8, 0.0, 1, 1.0, clip, skip), {})
+
+
+def host(n, dtype=torch.float32):
+    return torch.zeros(n, dtype=dtype)
+
+
+def strided(n, make=f32):
+    """n elements at stride 2, starting on an allocation boundary: only contiguity is wrong."""
+    return make(2 * n)[::2]
+
+
+def _flat_optim_cases():
+    """One row per device / contiguity / size / alignment check of the flat optimizer ops; every
+    other argument of a row is valid, so the named check is the one that refuses it."""
+    return [
+        ("sqnorm-host-partial", "sqnorm", lambda: ((f32(8), host(4), f32(3), 1.0, 1.0), {}), "raises"),
+        ("sqnorm-host-out", "sqnorm", lambda: ((f32(8), f32(4), host(3), 1.0, 1.0), {}), "raises"),
+        ("sqnorm-strided-partial", "sqnorm", lambda: ((f32(8), strided(4), f32(3), 1.0, 1.0), {}), "raises"),
+        ("sqnorm-strided-out", "sqnorm", lambda: ((f32(8), f32(4), strided(3), 1.0, 1.0), {}), "raises"),
+        ("sqnorm-empty-partial", "sqnorm", lambda: ((f32(8), f32(0), f32(3), 1.0, 1.0), {}), "raises"),
+        ("adamw_ema-host-clip", "adamw_ema", lambda: _adamw(clip=host(3)), "raises"),
+        ("adamw_ema-strided-clip", "adamw_ema", lambda: _adamw(clip=strided(3)), "raises"),
+        ("adamw_ema-clip-1-float", "adamw_ema", lambda: _adamw(clip=f32(1)), "raises"),
+        ("adamw_ema-host-ema", "adamw_ema", lambda: _adamw(ema_list=[host(8)]), "raises"),
+        ("adamw_ema-host-shadow", "adamw_ema", lambda: _adamw(shadow=host(8, torch.bfloat16)), "raises"),
+        ("ema_update-host-ema", "ema_update", lambda: ((host(8), f32(8), 0.5), {}), "raises"),
+        ("ema_update-host-param", "ema_update", lambda: ((f32(8), host(8), 0.5), {}), "raises"),
+        ("ema_update-strided-ema", "ema_update", lambda: ((strided(8), f32(8), 0.5), {}), "raises"),
+        ("ema_update-strided-param", "ema_update", lambda: ((f32(8), strided(8), 0.5), {}), "raises"),
+        ("cast_bf16-host-src", "cast_bf16", lambda: ((host(8), bf(8)), {}), "raises"),
+        ("cast_bf16-host-dst", "cast_bf16", lambda: ((f32(8), host(8, torch.bfloat16)), {}), "raises"),
+        ("cast_bf16-strided-src", "cast_bf16", lambda: ((strided(8), bf(8)), {}), "raises"),
+        ("cast_bf16-strided-dst", "cast_bf16", lambda: ((f32(8), strided(8, bf)), {}), "raises"),
+        # 4 bytes past an 8-byte boundary: the kernel stores 4 bf16 as one 8-byte word
+        ("cast_bf16-dst-4B-aligned", "cast_bf16", lambda: ((f32(8), bf(12)[2:10]), {}), "raises"),
+    ]
 
 
 def _reverse(N=4, E=8, **kw):
@@ -120,6 +157,7 @@ CASES = [
     ("adamw_ema-emas-vs-rates", "adamw_ema", lambda: _adamw(emas=2, rates=1), "raises"),
     ("adamw_ema-i64-skip", "adamw_ema", lambda: _adamw(skip=i64(1)), "raises"),
     ("sqnorm-out-2", "sqnorm", lambda: ((f32(8), f32(4), f32(2), 1.0, 1.0), {}), "raises"),
+    *_flat_optim_cases(),
     ("sample_tokens-temperature-0", "sample_tokens", lambda: ((f32(2, 64), 0.0, 0, 1.0, 1, 0, 0), {}), "raises"),
     # declines
     ("attn_decode-head_dim-32", "attn_decode",
