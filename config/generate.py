@@ -45,6 +45,14 @@ class ContinueSettings(S):
                      "depends on the batching). philox: counter-based noise keyed by (seed, step, sample index "
                      "in the split, token id), so a row's draws do not depend on the batching; on a GPU the "
                      "choice of the next token is then one fused kernel per step.")
+    num_beams: int \
+        = _(1, "Beam search with this many beams per prompt (1 = off: greedy or sampling as above). Beam "
+               "search ignores temperature and seed, and excludes top_k, top_p and --noise philox.")
+    length_penalty: float \
+        = _(0.0, "Beam search: the beams of a prompt are ordered by score / length ** length_penalty "
+                 "(0 = the raw sum of log-probabilities).")
+    keep_beams: bool \
+        = _(False, "Beam search: also write 'beams' (every beam's ids, best first) and 'beam_scores'.")
     out_path: str \
         = _("", "Output .jsonl file (default: generated_<checkpoint>_seed<seed>.jsonl next to the checkpoint).")
     precision: Choice("bf16", "fp32") \
@@ -89,6 +97,18 @@ class GenerateSettings(
             raise ValueError(f"--temperature must be >= 0, got {self.temperature}")
         if self.top_k < 0:
             raise ValueError(f"--top_k must be >= 0, got {self.top_k}")
+        if self.num_beams < 1:
+            raise ValueError(f"--num_beams must be >= 1, got {self.num_beams}")
+        if self.num_beams > 1:
+            if self.num_beams > 255:
+                raise ValueError(f"--num_beams must be <= 255 (one byte per cache table entry), got {self.num_beams}")
+            if self.top_k != 0 or self.top_p != 0.0 or self.noise == "philox":
+                raise ValueError("--num_beams > 1 is a deterministic search: it excludes --top_k, --top_p and "
+                                 "--noise philox")
+            # the decode attention's grid is rows x heads workgroups, below 2^31
+            if self.num_beams * self.batch_size > 0x7FFFFFFF // max(self.num_heads, 64):
+                raise ValueError(f"--num_beams {self.num_beams} x --batch_size {self.batch_size} cache rows "
+                                 "cannot be addressed")
         if self.prompt_len < 1 or self.max_new_tokens < 1:
             raise ValueError("--prompt_len and --max_new_tokens must be >= 1")
         if self.prompt_len + self.max_new_tokens > self.seq_len:

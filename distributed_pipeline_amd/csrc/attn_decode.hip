@@ -23,7 +23,15 @@
 //
 // The grid is B * H workgroups; there is no split over keys across workgroups, so a small batch
 // does not fill the chip.
+//
+// The AdTable instantiations are the same step for beam search: rows come in groups of W (row
+// b W + w is slot w of prompt b) and a uint8 table src [B][Lmax] names, per row and cached position,
+// the slot of the row's group that holds that key - hypotheses are re-parented by rewriting W Lmax
+// bytes per prompt instead of gathering the caches.  The AdNoTable instantiations carry none of
+// it: their instruction stream is what it was without the table.
 #include <math.h>
+
+#include <type_traits>
 
 #include "common.h"
 #include "launchers.h"
@@ -82,11 +90,27 @@ __device__ __forceinline__ void ad_update(AdState& st, const float s[N], const u
   st.m = mn;
 }
 
-template <int D>
+// TAB = AdTable: cached key t of row b is read from cache row (b / W) W + min(src[b][t], W - 1) - a
+// slot of the row's own group of W rows, whatever the byte - while the append still goes to the
+// row's own slot.  The table bytes of an iteration are fetched one iteration ahead of its K/V loads
+// (which depend on them), beside the ping-pong prefetch: a wave load is then KPW rows of 2 D bytes,
+// each anywhere in the group, instead of 1 KB contiguous.  The fold order over keys, lane groups and
+// waves is the same, so an identity table gives the plain kernel's bits.  Caller's contract: no
+// active row reads a (slot, position) that another active row of the same call appends to (true
+// whenever the active rows of a group have equal lens).
+struct AdNoTable {};
+struct AdTable {
+  const uint8_t* src;  // [B][Lmax] bytes, rows `stride` apart
+  int64_t stride;
+  int W;
+};
+
+template <int D, typename TAB>
 __global__ void __launch_bounds__(64 * AD_WAVES) attn_decode_kernel(
     const bf16_t* __restrict__ qkv, int64_t qkv_stride, bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
     int64_t k_sb, int64_t k_sh, int64_t v_sb, int64_t v_sh, const int* __restrict__ lens, int H, int Lmax,
-    bf16_t* __restrict__ out) {
+    bf16_t* __restrict__ out, TAB tab) {
+  constexpr bool BEAM = !std::is_same<TAB, AdNoTable>::value;
   constexpr int G = D / 8;               // lanes per key row
   constexpr int KPW = 64 / G;            // keys per wave load
   constexpr int U = AD_U;
@@ -152,7 +176,59 @@ __global__ void __launch_bounds__(64 * AD_WAVES) attn_decode_kernel(
   };
 
   int base = wave * WK;  // wave-uniform, as is every branch on it
-  if (base < n) {
+  if constexpr (BEAM) {
+    const int W = tab.W;
+    const int gb = b / W * W;  // the group's first cache row
+    const bf16_t* kg = kc + (int64_t)gb * k_sb + (int64_t)h * k_sh + c * 8;
+    const bf16_t* vg = vc + (int64_t)gb * v_sb + (int64_t)h * v_sh + c * 8;
+    const uint8_t* srow = tab.src + (int64_t)b * tab.stride;
+    // Every load of this variant is unconditional, on a key clamped to n - 1: a lane whose key lies
+    // at or beyond n reads the byte and the rows of key n - 1 (never anything at or beyond n) and the
+    // fold gives them weight 0, as it gives the zeros of the plain kernel.  Without a branch around
+    // each load the compiler counts the loads in flight exactly, instead of draining them in front
+    // of every dependent load.
+    auto slots = [&](int base, int sl[U]) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) sl[u] = (int)srow[min(base + u * KPW + g, n - 1)];
+    };
+    auto gload = [&](int base, const int sl[U], uint4 kr[U], uint4 vr[U]) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int key = min(base + u * KPW + g, n - 1);
+        const int slot = min(sl[u], W - 1);  // inside the group, whatever the table holds
+        kr[u] = *reinterpret_cast<const uint4*>(kg + (int64_t)slot * k_sb + (int64_t)key * D);
+        vr[u] = *reinterpret_cast<const uint4*>(vg + (int64_t)slot * v_sb + (int64_t)key * D);
+      }
+    };
+    if (base < n) {  // n >= 1
+      // Loads return in issue order, so the bytes an iteration's K/V loads wait for must be older
+      // than the K/V loads in flight: the bytes of iteration i + 2 are issued in front of the K/V
+      // loads of iteration i + 1 (two byte sets, ping-pong like the K/V sets).  Issued behind them,
+      // the wait for the bytes would drain the K/V loads too - one exposed memory latency per
+      // iteration instead of half of one.  The loads of the iterations past the end (clamped, all
+      // on key n - 1) are issued and never used.
+      uint4 ka[U], va[U], kb2[U], vb2[U];
+      int sla[U], slb[U];
+      slots(base, slb);
+      slots(base + IT, sla);
+      __builtin_amdgcn_sched_barrier(0);
+      gload(base, slb, ka, va);
+      for (;;) {
+        slots(base + 2 * IT, slb);
+        __builtin_amdgcn_sched_barrier(0);
+        gload(base + IT, sla, kb2, vb2);
+        fold(base, ka, va);
+        base += IT;
+        if (base >= n) break;
+        slots(base + 2 * IT, sla);
+        __builtin_amdgcn_sched_barrier(0);
+        gload(base + IT, slb, ka, va);
+        fold(base, kb2, vb2);
+        base += IT;
+        if (base >= n) break;
+      }
+    }
+  } else if (base < n) {
     uint4 ka[U], va[U], kb2[U], vb2[U];
     load(base, ka, va);
     for (;;) {
@@ -211,20 +287,45 @@ __global__ void __launch_bounds__(64 * AD_WAVES) attn_decode_kernel(
   }
 }
 
-bool launch_attn_decode(const uint16_t* qkv_new, int64_t qkv_stride, uint16_t* k_cache, uint16_t* v_cache,
-                        int64_t k_sb, int64_t k_sh, int64_t v_sb, int64_t v_sh, const int* lens, int B, int H,
-                        int Lmax, int D, uint16_t* out, hipStream_t s) {
+static bool ad_args_ok(const uint16_t* qkv_new, int64_t qkv_stride, const uint16_t* k_cache, const uint16_t* v_cache,
+                       int64_t k_sb, int64_t k_sh, int64_t v_sb, int64_t v_sh, const int* lens, int B, int H,
+                       int Lmax, int D, const uint16_t* out) {
   if ((D != 64 && D != 128) || B <= 0 || H <= 0 || Lmax <= 0 || (int64_t)B * H > 0x7fffffffLL) return false;
   if (!qkv_new || !k_cache || !v_cache || !lens || !out) return false;
   // 16-byte rows: every row start is a multiple of 8 elements from a 16-byte aligned base
-  if (qkv_stride % 8 || k_sb % 8 || k_sh % 8 || v_sb % 8 || v_sh % 8) return false;
+  return !(qkv_stride % 8 || k_sb % 8 || k_sh % 8 || v_sb % 8 || v_sh % 8);
+}
+
+bool launch_attn_decode_beam(const uint16_t* qkv_new, int64_t qkv_stride, uint16_t* k_cache, uint16_t* v_cache,
+                             int64_t k_sb, int64_t k_sh, int64_t v_sb, int64_t v_sh, const int* lens,
+                             const uint8_t* src, int64_t src_stride, int W, int B, int H, int Lmax, int D,
+                             uint16_t* out, hipStream_t s) {
+  if (!ad_args_ok(qkv_new, qkv_stride, k_cache, v_cache, k_sb, k_sh, v_sb, v_sh, lens, B, H, Lmax, D, out))
+    return false;
+  if (!src || W < 1 || W > 255 || B % W || src_stride < Lmax || Lmax > (1 << 30)) return false;
+  const dim3 grid((unsigned)(B * H)), block(64 * AD_WAVES);
+  const AdTable tab{src, src_stride, W};
+  if (D == 64)
+    hipLaunchKernelGGL((attn_decode_kernel<64, AdTable>), grid, block, 0, s, qkv_new, qkv_stride, k_cache, v_cache,
+                       k_sb, k_sh, v_sb, v_sh, lens, H, Lmax, out, tab);
+  else
+    hipLaunchKernelGGL((attn_decode_kernel<128, AdTable>), grid, block, 0, s, qkv_new, qkv_stride, k_cache, v_cache,
+                       k_sb, k_sh, v_sb, v_sh, lens, H, Lmax, out, tab);
+  return true;
+}
+
+bool launch_attn_decode(const uint16_t* qkv_new, int64_t qkv_stride, uint16_t* k_cache, uint16_t* v_cache,
+                        int64_t k_sb, int64_t k_sh, int64_t v_sb, int64_t v_sh, const int* lens, int B, int H,
+                        int Lmax, int D, uint16_t* out, hipStream_t s) {
+  if (!ad_args_ok(qkv_new, qkv_stride, k_cache, v_cache, k_sb, k_sh, v_sb, v_sh, lens, B, H, Lmax, D, out))
+    return false;
   const dim3 grid((unsigned)(B * H)), block(64 * AD_WAVES);
   if (D == 64)
-    hipLaunchKernelGGL(attn_decode_kernel<64>, grid, block, 0, s, qkv_new, qkv_stride, k_cache, v_cache, k_sb, k_sh,
-                       v_sb, v_sh, lens, H, Lmax, out);
+    hipLaunchKernelGGL((attn_decode_kernel<64, AdNoTable>), grid, block, 0, s, qkv_new, qkv_stride, k_cache, v_cache,
+                       k_sb, k_sh, v_sb, v_sh, lens, H, Lmax, out, AdNoTable{});
   else
-    hipLaunchKernelGGL(attn_decode_kernel<128>, grid, block, 0, s, qkv_new, qkv_stride, k_cache, v_cache, k_sb, k_sh,
-                       v_sb, v_sh, lens, H, Lmax, out);
+    hipLaunchKernelGGL((attn_decode_kernel<128, AdNoTable>), grid, block, 0, s, qkv_new, qkv_stride, k_cache, v_cache,
+                       k_sb, k_sh, v_sb, v_sh, lens, H, Lmax, out, AdNoTable{});
   return true;
 }
 

@@ -90,8 +90,13 @@ static std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor
 // bf16, k_cache / v_cache [B, H, Lmax, D] bf16 (updated in place; batch and head strides free, so
 // views into a larger buffer work), lens [B] int32 -> out [B, H D] bf16, or None for a case the
 // kernel does not cover (dtype, D, CPU tensors, row layout): the caller's PyTorch path takes it.
-static c10::optional<at::Tensor> attn_decode(const at::Tensor& qkv_new, at::Tensor& k_cache, at::Tensor& v_cache,
-                                             const at::Tensor& lens, int64_t n_heads) {
+//
+// With `src` (attn_decode_beam): the rows are groups of `beams` slots and src uint8 [B, Lmax] names the
+// slot of the row's group that holds each cached key (launchers.h has the semantics and the caller's
+// contract).
+static c10::optional<at::Tensor> attn_decode_any(const at::Tensor& qkv_new, at::Tensor& k_cache, at::Tensor& v_cache,
+                                                 const at::Tensor& lens, int64_t n_heads, const at::Tensor* src,
+                                                 int64_t beams) {
   TORCH_CHECK(qkv_new.dim() == 2 && k_cache.dim() == 4 && v_cache.dim() == 4 && lens.dim() == 1 && n_heads > 0,
               "attn_decode: qkv_new [B, 3 H D], caches [B, H, Lmax, D], lens [B]");
   const int64_t B = k_cache.size(0), H = k_cache.size(1), Lmax = k_cache.size(2), D = k_cache.size(3);
@@ -99,6 +104,14 @@ static c10::optional<at::Tensor> attn_decode(const at::Tensor& qkv_new, at::Tens
                   qkv_new.size(1) == 3 * H * D && lens.size(0) == B,
               "attn_decode: shapes of qkv_new, the caches, lens and n_heads do not agree");
   TORCH_CHECK(lens.scalar_type() == at::kInt, "attn_decode: lens must be int32");
+  if (src) {
+    TORCH_CHECK(src->scalar_type() == at::kByte, "attn_decode_beam: src must be uint8");
+    TORCH_CHECK(src->dim() == 2 && src->size(0) == B && src->size(1) == Lmax, "attn_decode_beam: src must be [R, Lmax]");
+    TORCH_CHECK(src->stride(1) == 1 || Lmax <= 1, "attn_decode_beam: src must have last stride 1");
+    TORCH_CHECK(beams >= 1 && beams <= 255, "attn_decode_beam: beams must be in 1 .. 255");
+    TORCH_CHECK(B % beams == 0, "attn_decode_beam: the rows must be whole groups of `beams`");
+    if (!src->is_cuda() || src->device() != qkv_new.device() || (B > 1 && src->stride(0) < Lmax)) return c10::nullopt;
+  }
   for (const at::Tensor* t : {&qkv_new, (const at::Tensor*)&k_cache, (const at::Tensor*)&v_cache, &lens})
     if (!t->is_cuda() || t->device() != qkv_new.device()) return c10::nullopt;
   if (qkv_new.scalar_type() != at::kBFloat16 || k_cache.scalar_type() != at::kBFloat16 ||
@@ -114,12 +127,27 @@ static c10::optional<at::Tensor> attn_decode(const at::Tensor& qkv_new, at::Tens
     return c10::nullopt;
   const c10::DeviceGuard guard(qkv_new.device());
   at::Tensor out = at::empty({B, H * D}, qkv_new.options());
-  const bool ok = dpa::launch_attn_decode(
-      bf_ptr(qkv_new), qkv_new.stride(0), bf_mut(k_cache), bf_mut(v_cache), k_cache.stride(0), k_cache.stride(1),
-      v_cache.stride(0), v_cache.stride(1), lens.data_ptr<int>(), (int)B, (int)H, (int)Lmax, (int)D, bf_mut(out),
-      cur_stream());
+  const bool ok =
+      src ? dpa::launch_attn_decode_beam(bf_ptr(qkv_new), qkv_new.stride(0), bf_mut(k_cache), bf_mut(v_cache),
+                                         k_cache.stride(0), k_cache.stride(1), v_cache.stride(0), v_cache.stride(1),
+                                         lens.data_ptr<int>(), src->data_ptr<uint8_t>(), B > 1 ? src->stride(0) : Lmax,
+                                         (int)beams, (int)B, (int)H, (int)Lmax, (int)D, bf_mut(out), cur_stream())
+          : dpa::launch_attn_decode(bf_ptr(qkv_new), qkv_new.stride(0), bf_mut(k_cache), bf_mut(v_cache),
+                                    k_cache.stride(0), k_cache.stride(1), v_cache.stride(0), v_cache.stride(1),
+                                    lens.data_ptr<int>(), (int)B, (int)H, (int)Lmax, (int)D, bf_mut(out), cur_stream());
   if (!ok) return c10::nullopt;
   return out;
+}
+
+static c10::optional<at::Tensor> attn_decode(const at::Tensor& qkv_new, at::Tensor& k_cache, at::Tensor& v_cache,
+                                             const at::Tensor& lens, int64_t n_heads) {
+  return attn_decode_any(qkv_new, k_cache, v_cache, lens, n_heads, nullptr, 1);
+}
+
+static c10::optional<at::Tensor> attn_decode_beam(const at::Tensor& qkv_new, at::Tensor& k_cache,
+                                                  at::Tensor& v_cache, const at::Tensor& lens, int64_t n_heads,
+                                                  const at::Tensor& src, int64_t beams) {
+  return attn_decode_any(qkv_new, k_cache, v_cache, lens, n_heads, &src, beams);
 }
 
 void dpa::register_attention(pybind11::module& m) {
@@ -138,4 +166,8 @@ void dpa::register_attention(pybind11::module& m) {
   m.def("attn_decode", &attn_decode,
         "KV-cache append + single-query attention of one decode step (caches updated in place) -> out [B, H D] bf16 | None (case not covered)",
         py::arg("qkv_new"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"), py::arg("n_heads"));
+  m.def("attn_decode_beam", &attn_decode_beam,
+        "attn_decode through a cache indirection table: rows in groups of `beams`, src uint8 [R, Lmax] names the group slot holding each cached key -> out [R, H D] bf16 | None (case not covered)",
+        py::arg("qkv_new"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"), py::arg("n_heads"),
+        py::arg("src"), py::arg("beams"));
 }

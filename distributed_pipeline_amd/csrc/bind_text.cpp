@@ -1,5 +1,8 @@
-// Bindings of the generation and text-metric kernels: token sampling (sample.hip) and the
+// Bindings of the generation and text-metric kernels: token sampling (sample.hip), the beam-search
+// step (beam_step.hip) and the
 // per-group n-gram / LCS counts (ngram_match.hip, ngram_distinct.hip, lcs.hip).
+#include <limits.h>
+
 #include "bind_util.h"
 
 // One next-token draw per row of logits [B, V] (csrc/sample.hip; the definition is in ops/decode.py):
@@ -43,6 +46,44 @@ static c10::optional<at::Tensor> sample_uniforms(const at::Tensor& like, int64_t
   if (!dpa::launch_sample_uniforms(out.data_ptr<float>(), B, (int)V, (uint64_t)seed, (uint32_t)step,
                                    (uint64_t)row_base, cur_stream()))
     return c10::nullopt;
+  return out;
+}
+
+// One beam-search step (csrc/beam_step.hip; the definition is in ops/decode.py): logits [B, W, V] fp32 or
+// bf16 (last stride 1, any batch / beam stride >= 0), scores fp32 [B, W], finished bool [B, W] ->
+// [new_scores fp32, parent int32, token int64, new_finished bool, logp fp32], all [B, W] (logp: a live
+// pick's own log-probability term, 0 for a finished beam's candidate and an empty slot); None for a case the
+// kernel does not cover (CPU tensor, dtype, V > 65536, W > 8, a last stride other than 1, B == 0).
+static c10::optional<std::vector<at::Tensor>> beam_step(const at::Tensor& logits, const at::Tensor& scores,
+                                                        const at::Tensor& finished, int64_t eos_id, int64_t fill) {
+  TORCH_CHECK(logits.dim() == 3, "beam_step: logits [B, W, V]");
+  const int64_t B = logits.size(0), W = logits.size(1), V = logits.size(2);
+  TORCH_CHECK(scores.dim() == 2 && scores.size(0) == B && scores.size(1) == W && finished.sizes() == scores.sizes(),
+              "beam_step: scores and finished must be [B, W]");
+  TORCH_CHECK(scores.scalar_type() == at::kFloat, "beam_step: scores must be float32");
+  TORCH_CHECK(finished.scalar_type() == at::kBool, "beam_step: finished must be bool");
+  if (!logits.is_cuda() || (logits.scalar_type() != at::kFloat && logits.scalar_type() != at::kBFloat16))
+    return c10::nullopt;
+  if (scores.device() != logits.device() || finished.device() != logits.device() || !scores.is_contiguous() ||
+      !finished.is_contiguous())
+    return c10::nullopt;
+  if (B < 1 || W < 1 || W > 8 || V < 1 || V > 65536 || B * W > 0x7fffffffLL || (V > 1 && logits.stride(2) != 1) ||
+      logits.stride(0) < 0 || logits.stride(1) < 0 || fill < INT_MIN || fill > INT_MAX)
+    return c10::nullopt;
+  const c10::DeviceGuard guard(logits.device());
+  auto opt = at::TensorOptions().device(logits.device());
+  std::vector<at::Tensor> out{at::empty({B, W}, opt.dtype(at::kFloat)), at::empty({B, W}, opt.dtype(at::kInt)),
+                              at::empty({B, W}, opt.dtype(at::kLong)), at::empty({B, W}, opt.dtype(at::kBool)),
+                              at::empty({B, W}, opt.dtype(at::kFloat))};
+  at::Tensor ws_c = at::empty({B, W, W + 2}, opt.dtype(at::kFloat)), ws_v = at::empty({B, W, W}, opt.dtype(at::kInt));
+  const int eos = (eos_id < 0 || eos_id > INT_MAX) ? -1 : (int)eos_id;
+  const bool ok = dpa::launch_beam_step(
+      logits.data_ptr(), logits.scalar_type() == at::kBFloat16, logits.stride(0), logits.stride(1), B, (int)W, (int)V,
+      scores.data_ptr<float>(), reinterpret_cast<const uint8_t*>(finished.data_ptr<bool>()), eos, (int)fill,
+      ws_c.data_ptr<float>(), ws_v.data_ptr<int>(), out[0].data_ptr<float>(), out[1].data_ptr<int>(),
+      out[2].data_ptr<int64_t>(), reinterpret_cast<uint8_t*>(out[3].data_ptr<bool>()), out[4].data_ptr<float>(),
+      cur_stream());
+  if (!ok) return c10::nullopt;
   return out;
 }
 
@@ -104,6 +145,9 @@ void dpa::register_text(pybind11::module& m) {
   m.def("sample_uniforms", &sample_uniforms,
         "the uniforms of sample_tokens -> fp32 [B, V] | None (case not covered)", py::arg("like"), py::arg("seed"),
         py::arg("step"), py::arg("row_base"), py::arg("B"), py::arg("V"));
+  m.def("beam_step", &beam_step,
+        "one beam-search step: log-softmax + cumulative score + the W best of W V candidates -> [new_scores, parent, token, new_finished, logp] | None (case not covered)",
+        py::arg("logits"), py::arg("scores"), py::arg("finished"), py::arg("eos_id") = -1, py::arg("fill") = 0);
   m.def("ngram_matches", &ngram_matches,
         "clipped 1..4-gram match counts of every sequence pair of a group -> int32 [G, K, K, 4] | None (shape not covered)",
         py::arg("tokens"), py::arg("lens"));

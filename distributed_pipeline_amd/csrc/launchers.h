@@ -221,6 +221,33 @@ bool launch_reverse_step(const float* x, const uint16_t* pred, const int64_t* id
 bool launch_attn_decode(const uint16_t* qkv_new, int64_t qkv_stride, uint16_t* k_cache, uint16_t* v_cache,
                         int64_t k_sb, int64_t k_sh, int64_t v_sb, int64_t v_sh, const int* lens, int B, int H,
                         int Lmax, int D, uint16_t* out, hipStream_t s);
+// The same step through a cache indirection table (beam search): rows in groups of W (B % W == 0),
+// src uint8 [B][Lmax] with rows src_stride bytes apart; active row b reads cached key t < lens[b] from
+// cache row (b / W) W + min(src[b][t], W - 1) and appends at its own (b, lens[b]).  src is not
+// modified and src[b][t], t >= lens[b], is never read.  With src[b][t] == b % W everywhere the results
+// are launch_attn_decode's bit for bit.  The caller guarantees that no active row reads a (slot,
+// position) another active row of the call appends to (equal lens within a group's active rows).
+// false, with no launch: as above, or W outside 1 .. 255, B % W != 0, src_stride < Lmax, Lmax > 2^30.
+bool launch_attn_decode_beam(const uint16_t* qkv_new, int64_t qkv_stride, uint16_t* k_cache, uint16_t* v_cache,
+                             int64_t k_sb, int64_t k_sh, int64_t v_sb, int64_t v_sh, const int* lens,
+                             const uint8_t* src, int64_t src_stride, int W, int B, int H, int Lmax, int D,
+                             uint16_t* out, hipStream_t s);
+
+// ---- beam_step.hip: log-softmax + score + top-W of W V candidates (beam search) ----------
+// logits [B][W][V] fp32 or bf16 (element strides stride_b, stride_w >= 0 - 0 repeats a row - and 1),
+// scores fp32 [B][W], finished bytes [B][W] -> the first W candidates of each b in the order
+// (descending c, ascending beam, ascending id): a live beam's c(w, v) = scores + ((s_v - max) - log Z),
+// a finished beam's one candidate (w, fill) at its score, none for a beam at -inf or a row whose
+// maximum is not finite.  new_scores fp32, parent int32, token int64, new_finished bytes, all [B][W];
+// slots without a candidate hold (-inf, 0, fill, 0).  logp (may be null) fp32 [B][W]: a live pick's own
+// term (s_v - max) - log Z, the bits that went into its c; 0 for a finished beam's candidate and an
+// empty slot.  Workspace: ws_c B W (W + 2) floats, ws_v B W W ints.
+// Two launches, no atomics.  false, with no launch: W outside 1 .. 8, V outside 1 .. 65536, B < 1, a
+// negative stride or a null pointer.
+bool launch_beam_step(const void* logits, bool bf16, int64_t stride_b, int64_t stride_w, int64_t B, int W, int V,
+                      const float* scores, const uint8_t* finished, int eos_id, int fill, float* ws_c, int* ws_v,
+                      float* new_scores, int* parent, int64_t* token, uint8_t* new_finished, float* logp,
+                      hipStream_t st);
 
 // ---- sample.hip: temperature / top-k / top-p next-token draw (GPT-2 generation) ---------
 // tokens[b] = the id drawn for row b of logits ([B][V] fp32 or bf16, rows row_stride elements apart, any

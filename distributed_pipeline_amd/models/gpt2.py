@@ -113,10 +113,12 @@ class GPT2LMModel(nn.Module):
         return ops.linear(last, self.wte.weight)
 
     @torch.no_grad()
-    def decode_step(self, tokens, cache):
+    def decode_step(self, tokens, cache, table=None):
         """One token per row at position ``cache.lens[b]`` -> the next-token logits [B, V];
         ``cache.lens`` advances on the device.  A parked row (``lens`` outside 0 .. max_len - 1)
-        does no cache work, keeps its ``lens``, and its logits mean nothing."""
+        does no cache work, keeps its ``lens``, and its logits mean nothing.  ``table``: a pair
+        ``(src uint8 [B, max_len], beams)`` handed to ``attention_decode`` - the rows are groups
+        of ``beams`` slots that read their cached keys through ``src`` (beam search)."""
         from ..ops.decode import attention_decode
         dt = self.compute_dtype
         B = tokens.shape[0]
@@ -128,8 +130,10 @@ class GPT2LMModel(nn.Module):
         x, a = ops.residual_layernorm(self.wte(tokens.view(1, B), dt), None, ln0.weight, ln0.bias, 0.0, ln0.eps,
                                       False, pos=self.wpe(pos, dt))
 
+        kw = {} if table is None else {"src": table[0], "beams": table[1]}
+
         def attend(i, qkv):
-            return attention_decode(qkv.view(B, -1), cache.k[i], cache.v[i], cache.lens, heads).view(1, B, -1)
+            return attention_decode(qkv.view(B, -1), cache.k[i], cache.v[i], cache.lens, heads, **kw).view(1, B, -1)
 
         a = self._blocks(x, a, attend)
         cache.lens += ((cache.lens >= 0) & (cache.lens < cache.max_len)).to(cache.lens.dtype)
@@ -184,10 +188,107 @@ class GPT2LMModel(nn.Module):
         cache.lens.masked_fill_(done, -1)
         return out, new_lens
 
+    @torch.no_grad()
+    def beam_search(self, input_ids, lens, max_new_tokens, *, num_beams, eos_id=None, length_penalty=0.0,
+                    cache=None, check_every=16):
+        """Continue right-padded prompts with beam search -> (tokens [B, W, max_new_tokens], new_lens
+        [B, W], scores fp32 [B, W]), ``W = num_beams``, the beams of a prompt best first.
+
+        The cache has ``B W`` rows, row ``b W + w`` being slot w of prompt b.  The prompts are
+        prefilled once, into slot 0 of each group; a uint8 table [B, W, max_len] names, per slot and
+        position, the slot that holds the key (``ops.decode.attention_decode``'s ``src``), starts as
+        zeros - every beam reads the one copy of the prompt - and is what a step re-parents instead
+        of the cache.  Step t: ``ops.decode.beam_step`` on the current logits; the next table is the
+        parents' rows with the position of the last append pointing at the parent; finished and
+        non-existent slots are parked; one ``decode_step`` through the table.
+
+        The search ranks by the cumulative log-probability alone, ``beam_step``'s fp32 sums (a
+        finished beam keeps its score and its place).  The returned ``scores`` are the raw sums of
+        the hypotheses' log-probabilities - ``beam_step``'s ``logp`` terms added up in float64 and
+        rounded to fp32 once, so they do not carry the rounding of every fp32 addition - and the
+        returned order is by ``scores / max(new_lens, 1) ** length_penalty`` (0: the raw sum), ties
+        to the lower slot.  As in
+        :meth:`generate`, a beam stops at ``eos_id`` or when the cache is full, the rest of its row
+        is ``eos_id`` (0 without one), ``new_lens`` counts a closing ``eos_id``, and the host looks
+        at the loop once every ``check_every`` steps (0: never).  A slot that never held a
+        hypothesis (fewer than W candidates) has score -inf, length 0 and a row of fill."""
+        from ..ops.decode import beam_step
+        W = int(num_beams)
+        if not 1 <= W <= 255:
+            raise ValueError(f"num_beams must be in 1 .. 255, got {num_beams}")
+        B, Lp = input_ids.shape
+        dev = input_ids.device
+        T = int(max_new_tokens)
+        if cache is None:
+            cache = self.init_cache(B * W, min(Lp + T, self.cfg["max_position_embeddings"]), dev)
+        elif cache.batch != B * W:
+            raise ValueError(f"beam search over {B} prompts x {W} beams needs a cache of {B * W} rows, "
+                             f"got {cache.batch}")
+        Lmax = cache.max_len
+        fill = 0 if eos_id is None else int(eos_id)
+        eos = -1 if eos_id is None else int(eos_id)
+        ninf = float("-inf")
+
+        logits = self.prefill(input_ids, lens, cache.slot_view(W, 0))  # the prompts, once, into slot 0
+        logits = logits.unsqueeze(1).expand(B, W, logits.shape[-1])    # beam stride 0
+        glen = lens.to(device=dev, dtype=torch.int32).clone()          # the group's common length
+        scores = torch.full((B, W), ninf, dtype=torch.float32, device=dev)
+        scores[:, 0] = 0.0
+        finished = torch.zeros(B, W, dtype=torch.bool, device=dev)
+        total = torch.zeros(B, W, dtype=torch.float64, device=dev)  # the hypotheses' summed log-probabilities
+        new_lens = torch.zeros(B, W, dtype=torch.long, device=dev)
+        tok_hist = torch.full((T, B, W), fill, dtype=torch.long, device=dev)
+        par_hist = torch.arange(W, device=dev).expand(T, B, W).contiguous()
+        tables = [torch.zeros(B, W, Lmax, dtype=torch.uint8, device=dev) for _ in range(2)]
+        cur = 0
+        cache.table = tables[cur]  # the table of the last decode step (zeros before the first)
+        exists = scores > ninf
+        active = exists
+        for t in range(T):
+            scores, parent, token, nfin, logp = beam_step(logits, scores, finished, eos_id=eos, fill=fill,
+                                                          return_logp=True)
+            par = parent.long()
+            total = total.gather(1, par) + logp.double()  # logp is 0 behind a finished beam
+            tok_hist[t], par_hist[t] = token, par
+            exists = scores > ninf
+            new_lens = torch.where(exists, new_lens.gather(1, par) + (~finished.gather(1, par)).long(), 0)
+            finished = nfin | (exists & (glen >= Lmax).view(B, 1))  # no room to run this token
+            active = exists & ~finished
+            if t + 1 == T:
+                break
+            if check_every and (t + 1) % check_every == 0 and not bool(active.any()):
+                break
+            # src'[b, j, :n] = src[b, parent[j], :n]; src'[b, j, n] = parent[j], n = the last appended position
+            nxt = tables[cur ^ 1]
+            torch.gather(tables[cur], 1, par.view(B, W, 1).expand(B, W, Lmax), out=nxt)
+            if t > 0:
+                at = (glen.long() - 1).clamp(0, Lmax - 1).view(B, 1, 1).expand(B, W, 1)
+                nxt.scatter_(2, at, parent.to(torch.uint8).view(B, W, 1))
+            cur ^= 1
+            cache.table = nxt
+            cache.lens.copy_(torch.where(active, glen.view(B, 1), -1).view(-1))
+            logits = self.decode_step(token.view(-1), cache, table=(nxt.view(B * W, Lmax), W)).view(B, W, -1)
+            glen = glen + (glen < Lmax).to(glen.dtype)
+        cache.lens.copy_(torch.where(active, glen.view(B, 1), -1).view(-1))
+
+        # the token rows: walk the recorded parents backwards
+        out = torch.full((B, W, T), fill, dtype=torch.long, device=dev)
+        idx = torch.arange(W, device=dev).expand(B, W)
+        for t in range(T - 1, -1, -1):
+            out[:, :, t] = tok_hist[t].gather(1, idx)
+            idx = par_hist[t].gather(1, idx)
+        out = torch.where(exists.unsqueeze(-1), out, fill)
+        scores = torch.where(exists, total.to(torch.float32), ninf)
+        key = scores / new_lens.clamp(min=1).to(torch.float32) ** float(length_penalty) if length_penalty else scores
+        order = torch.sort(key, dim=1, descending=True, stable=True).indices
+        out = out.gather(1, order.unsqueeze(-1).expand(B, W, T))
+        return out, new_lens.gather(1, order), scores.gather(1, order)
+
 
 class KVCache:
     """Per-layer K / V of shape [B, H, max_len, D] - views into one buffer - and ``lens`` int32
-    [B], the tokens cached per row (outside 0 .. max_len - 1: a parked row)."""
+    [B], the tokens cached per row (outside 0 .. max_len - 1: a parked row).  ``table``: after a
+    beam search, the uint8 [B / W, W, max_len] indirection table of its last decode step."""
 
     def __init__(self, layers, batch, heads, max_len, head_dim, device, dtype):
         self.batch, self.heads, self.max_len, self.head_dim = batch, heads, max_len, head_dim
@@ -195,6 +296,22 @@ class KVCache:
         self.k = [self.buf[i, 0] for i in range(layers)]
         self.v = [self.buf[i, 1] for i in range(layers)]
         self.lens = torch.zeros(batch, dtype=torch.int32, device=device)
+        self.table = None
+
+    def slot_view(self, beams, slot):
+        """The rows ``slot, slot + beams, ...`` as a cache of ``batch / beams`` rows over the same
+        storage (strided views; ``lens`` is the view's own): where ``prefill`` writes the prompts
+        of a beam search."""
+        if self.batch % beams:
+            raise ValueError(f"{self.batch} cache rows are not whole groups of {beams}")
+        view = KVCache.__new__(KVCache)
+        view.batch, view.heads, view.max_len, view.head_dim = self.batch // beams, self.heads, self.max_len, self.head_dim
+        view.buf = self.buf[:, :, slot::beams]
+        view.k = [k[slot::beams] for k in self.k]
+        view.v = [v[slot::beams] for v in self.v]
+        view.lens = self.lens[slot::beams]
+        view.table = None
+        return view
 
 
 def _gpt2_train_flops_per_sample(self, seq_len):

@@ -1,6 +1,6 @@
 """
-The two per-token ops of GPT-2 generation: single-query attention over a K/V cache, and the choice
-of the next token.
+The per-token ops of GPT-2 generation: single-query attention over a K/V cache (directly, or through
+the indirection table of a beam search), one beam-search step, and the choice of the next token.
 
 Attention of one decode step
 ----------------------------
@@ -21,6 +21,53 @@ rows beyond ``lens[b]`` never contribute, whatever they hold.
 bf16 on a HIP device with D in {64, 128}: one kernel (csrc/attn_decode.hip).  Anything else (CPU,
 fp32, other D, a cache whose rows are not packed): the same definition in fp32 PyTorch,
 :func:`attention_decode_ref`.  Inference only: no autograd.
+
+The cache indirection table (beam search).  With ``src`` (uint8 [R, Lmax]) and ``beams = W``
+(``R % W == 0``) the R rows are groups of W slots: row ``r = b W + w`` is slot w of prompt b.  An
+active row r reads its cached key and value ``t < lens[r]`` from cache row
+``(r // W) W + min(src[r, t], W - 1)`` - the clamp keeps any table content inside the row's own
+group, so a bad table gives wrong numbers and never an out-of-range read - while the new k and v are
+stored at ``(r, lens[r])``, the row's own slot.  ``src`` is not modified and ``src[r, t]`` for
+``t >= lens[r]`` is never read.  Inactive rows behave as without a table.  The fold order is the
+plain kernel's: with ``src[r, t] == r % W`` everywhere the output and the caches are the plain
+call's bit for bit.  Caller's contract: no active row may read a (slot, position) that another active
+row of the same call appends to; this holds whenever the active rows of a group have equal ``lens``,
+which is what beam search guarantees.  Re-parenting W hypotheses then rewrites ``W Lmax`` bytes per
+prompt instead of gathering ``[layers, 2, B W, H, Lmax, D]`` into a second buffer.
+
+One beam-search step: ``beam_step``
+-----------------------------------
+``beam_step(logits [B, W, V], scores fp32 [B, W], finished bool [B, W], *, eos_id=-1, fill=0)
+-> (new_scores fp32 [B, W], parent int32 [B, W], token int64 [B, W], new_finished bool [B, W])``.
+``logits`` is fp32 or bf16 with last stride 1 and any batch or beam stride; beam stride 0 is how the
+first step runs (the prefill logits ``[B, 1, V]`` expanded, ``scores = [0, -inf, ...]``).
+
+1. ``s_v = fp32(logit_v)``.  A NaN becomes -inf.
+2. A beam with ``scores[b, w] == -inf`` (or NaN) does not exist and has no candidate.
+3. A finished beam has exactly one candidate ``(w, fill)``, whose value is ``scores[b, w]`` with its
+   bits unchanged.
+4. A live beam has the candidates ``c(w, v) = scores[b, w] + ((s_v - m) - log Z)`` in fp32, in that
+   operation order, with ``m = max_v s_v`` and ``Z = sum_v exp(s_v - m)`` summed in one fixed order
+   per path (the kernel: per thread, then lanes, then waves; PyTorch: ``sum``), with the accurate
+   ``logf``.  A live beam whose ``m`` is not finite (all -inf, or any +inf) has no candidate.
+5. The result is the first W candidates in the order: descending ``c``, then ascending flat index
+   ``w V + v`` (lowest beam, then lowest id) - the repository's tie rule.
+6. A candidate with ``c == -inf`` (or NaN) is not a candidate.  Slots with no candidate left get
+   ``(-inf, parent 0, token fill, finished False)``.
+7. ``new_finished = finished[parent] | (token == eos_id)`` for the filled slots; ``eos_id < 0``: never.
+8. Every output is in range for any input: ``parent`` in ``[0, W)``, ``token`` in ``[0, V)`` or ``fill``.
+9. ``return_logp=True`` adds ``logp`` fp32 [B, W]: for a live beam's pick its own term
+   ``(s_v - m) - log Z`` - the bits that went into ``c``, so ``new_scores == scores[parent] + logp`` in
+   fp32 - and 0 for a finished beam's candidate and for an empty slot.  A caller that wants the sum
+   of a hypothesis' log-probabilities without the rounding of every fp32 addition adds these up in
+   float64 (``GPT2LMModel.beam_search`` does).
+
+On a HIP device with ``V <= 65536`` and ``W <= 8``: two launches of csrc/beam_step.hip (a row's top W
+per workgroup, then one wave per prompt merging the ``W W`` pairs - exact, since the global top W is
+contained in the union of the rows' top W under the same order), no ``[B W, V]`` tensor and nothing
+read back.  Anything else: :func:`beam_step_ref`, the same definition in PyTorch over chunks of
+rows.  The two paths may differ only in that a candidate value can differ by fp32 rounding, and in a
+pick where two candidates from different ``(w, s_v)`` lie within that rounding of each other.
 
 The next token: ``sample_tokens``
 ---------------------------------
@@ -72,11 +119,23 @@ _M32 = 0xFFFFFFFF
 _M64 = 0xFFFFFFFFFFFFFFFF
 
 
-def attention_decode_ref(qkv_new, k_cache, v_cache, lens, n_heads):
+def _check_table(src, beams, R, Lmax):
+    W = int(beams)
+    if not 1 <= W <= 255:
+        raise ValueError(f"beams must be in 1 .. 255, got {beams}")
+    if R % W:
+        raise ValueError(f"{R} cache rows are not whole groups of {W} beams")
+    if src.dtype != torch.uint8 or tuple(src.shape) != (R, Lmax):
+        raise ValueError(f"src must be uint8 [{R}, {Lmax}], got {src.dtype} {tuple(src.shape)}")
+    return W
+
+
+def attention_decode_ref(qkv_new, k_cache, v_cache, lens, n_heads, *, src=None, beams=1):
     """The definition in fp32 PyTorch (any device, any dtype); also the numerics yardstick of
-    the kernel's tests."""
+    the kernel's tests.  With ``src`` the effective caches of every row are gathered first."""
     B, H, Lmax, D = k_cache.shape
     assert H == n_heads and qkv_new.shape == (B, 3 * H * D) and lens.shape == (B,)
+    W = 1 if src is None else _check_table(src, beams, B, Lmax)
     q, k, v = qkv_new.detach().reshape(B, 3, H, D).unbind(1)
     n = lens.long()
     active = (n >= 0) & (n < Lmax)
@@ -86,26 +145,43 @@ def attention_decode_ref(qkv_new, k_cache, v_cache, lens, n_heads):
     # the append: an inactive row writes back what its slot already holds
     k_cache[rows, :, at] = torch.where(keep, k.to(k_cache.dtype), k_cache[rows, :, at])
     v_cache[rows, :, at] = torch.where(keep, v.to(v_cache.dtype), v_cache[rows, :, at])
-    mask = (torch.arange(Lmax, device=qkv_new.device).view(1, Lmax) <= at.view(B, 1)).view(B, 1, Lmax)
-    s = torch.einsum("bhd,bhld->bhl", q.float(), k_cache.float()) / math.sqrt(D)
+    pos = torch.arange(Lmax, device=qkv_new.device).view(1, Lmax)
+    mask = (pos <= at.view(B, 1)).view(B, 1, Lmax)
+    ke, ve = k_cache, v_cache
+    if src is not None:
+        # the slot each (row, position) is read from: the table's, clamped into the group, for the
+        # cached keys and the row's own for the key just appended (what lies behind is masked)
+        slot = torch.where(pos < at.view(B, 1), src.long().clamp(max=W - 1), (rows % W).view(B, 1))
+        from_row = (rows // W * W).view(B, 1) + slot
+        # [B, H, Lmax, D], packed like a whole cache: the sums below then run as on a gathered cache
+        ke = k_cache[from_row, :, pos].permute(0, 2, 1, 3).contiguous()
+        ve = v_cache[from_row, :, pos].permute(0, 2, 1, 3).contiguous()
+    s = torch.einsum("bhd,bhld->bhl", q.float(), ke.float()) / math.sqrt(D)
     p = torch.softmax(s.masked_fill(~mask, float("-inf")), -1)
-    vf = torch.where(mask.unsqueeze(-1), v_cache.float(), 0.0)  # a NaN beyond lens must not reach the sum
+    vf = torch.where(mask.unsqueeze(-1), ve.float(), 0.0)  # a NaN beyond lens must not reach the sum
     o = torch.einsum("bhl,bhld->bhd", p, vf)
     return torch.where(keep, o, 0.0).to(qkv_new.dtype).reshape(B, H * D)
 
 
 @torch.no_grad()
-def attention_decode(qkv_new, k_cache, v_cache, lens, n_heads):
-    """-> out [B, H*D] in ``qkv_new``'s dtype; ``k_cache`` / ``v_cache`` updated in place."""
+def attention_decode(qkv_new, k_cache, v_cache, lens, n_heads, *, src=None, beams=1):
+    """-> out [B, H*D] in ``qkv_new``'s dtype; ``k_cache`` / ``v_cache`` updated in place.
+    ``src`` uint8 [B, Lmax] with ``beams = W``: the cache indirection table of the module docstring."""
+    if src is not None:
+        _check_table(src, beams, k_cache.shape[0], k_cache.shape[2])
     if qkv_new.is_cuda:
         ext = get_ext()  # raises on a GPU without the built extension: no quiet fall-back
         if ext is not None:
             if qkv_new.stride(-1) != 1 or qkv_new.stride(0) % 8 or qkv_new.data_ptr() % 16:
                 qkv_new = qkv_new.contiguous()
-            out = ext.attn_decode(qkv_new, k_cache, v_cache, lens, int(n_heads))
+            if src is None:
+                out = ext.attn_decode(qkv_new, k_cache, v_cache, lens, int(n_heads))
+            else:
+                out = ext.attn_decode_beam(qkv_new, k_cache, v_cache, lens, int(n_heads),
+                                           src if src.stride(-1) == 1 else src.contiguous(), int(beams))
             if out is not None:
                 return out
-    return attention_decode_ref(qkv_new, k_cache, v_cache, lens, n_heads)
+    return attention_decode_ref(qkv_new, k_cache, v_cache, lens, n_heads, src=src, beams=beams)
 
 
 # ---- sample_tokens ------------------------------------------------------------------------------
@@ -235,3 +311,80 @@ def sample_tokens(logits, *, temperature, top_k=0, top_p=0.0, seed, step, row_ba
     out = sample_tokens_ref(logits, temperature=temperature, top_k=k, top_p=p, seed=seed, step=step,
                             row_base=row_base)
     return out if return_stats else out[0]
+
+
+# ---- beam_step ----------------------------------------------------------------------------------
+
+def _check_beam_step(logits, scores, finished):
+    if logits.dim() != 3:
+        raise ValueError(f"logits must be [B, W, V], got {tuple(logits.shape)}")
+    B, W, V = logits.shape
+    if W < 1 or V < 1:
+        raise ValueError(f"logits must have W >= 1 and V >= 1, got {tuple(logits.shape)}")
+    if tuple(scores.shape) != (B, W) or tuple(finished.shape) != (B, W):
+        raise ValueError(f"scores and finished must be [{B}, {W}], got {tuple(scores.shape)}, {tuple(finished.shape)}")
+    if scores.dtype != torch.float32 or finished.dtype != torch.bool:
+        raise ValueError(f"scores must be float32 and finished bool, got {scores.dtype}, {finished.dtype}")
+    return B, W, V
+
+
+@torch.no_grad()
+def beam_step_ref(logits, scores, finished, *, eos_id=-1, fill=0, chunk=64, return_logp=False):
+    """The definition in PyTorch (any device, any float dtype), at most ``chunk`` rows - one
+    ``[chunk, V]`` fp32 block - at a time."""
+    B, W, V = _check_beam_step(logits, scores, finished)
+    dev = logits.device
+    ninf = float("-inf")
+    k = min(W, V)
+    exists = scores > ninf  # False for a NaN too
+    cand_c = torch.full((B, W, W), ninf, dtype=torch.float32, device=dev)
+    cand_v = torch.zeros((B, W, W), dtype=torch.long, device=dev)
+    cand_lp = torch.zeros((B, W, W), dtype=torch.float32, device=dev)
+    step = max(1, int(chunk) // W)
+    for b0 in range(0, B, step):
+        s = logits[b0:b0 + step].float()  # [n, W, V]
+        s = torch.where(torch.isnan(s), ninf, s)
+        m = s.amax(-1, keepdim=True)
+        d = s - m
+        sc = scores[b0:b0 + step].unsqueeze(-1)
+        lp = d - torch.log(torch.exp(d).sum(-1, keepdim=True))
+        c = sc + lp
+        live = (exists[b0:b0 + step] & ~finished[b0:b0 + step]).unsqueeze(-1) & torch.isfinite(m)
+        c = torch.where(live & ~torch.isnan(c), c, ninf)
+        # a stable sort keeps equal values in id order
+        top, idx = torch.sort(c, dim=-1, descending=True, stable=True)
+        cand_c[b0:b0 + step, :, :k] = top[..., :k]
+        cand_v[b0:b0 + step, :, :k] = idx[..., :k]
+        cand_lp[b0:b0 + step, :, :k] = lp.gather(-1, idx[..., :k])
+    own = exists & finished  # one candidate: (score, fill), bits unchanged
+    first = torch.zeros(W, dtype=torch.bool, device=dev)
+    first[0] = True
+    cand_c = torch.where(own.unsqueeze(-1), torch.where(first, scores.unsqueeze(-1), ninf), cand_c)
+    cand_v = torch.where(own.unsqueeze(-1), int(fill), cand_v)
+    # rows in beam order, a row's candidates in (c, id) order: a stable sort gives the tie rule
+    new_scores, at = torch.sort(cand_c.view(B, W * W), dim=-1, descending=True, stable=True)
+    new_scores, at = new_scores[:, :W], at[:, :W]
+    valid = new_scores > ninf
+    parent = torch.where(valid, at // W, 0)
+    token = torch.where(valid, cand_v.view(B, W * W).gather(1, at), int(fill))
+    new_finished = valid & (finished.gather(1, parent) | ((token == int(eos_id)) & (int(eos_id) >= 0)))
+    out = (new_scores, parent.to(torch.int32), token, new_finished)
+    if return_logp:
+        live = valid & ~finished.gather(1, parent)
+        out += (torch.where(live, cand_lp.view(B, W * W).gather(1, at), 0.0),)
+    return out
+
+
+@torch.no_grad()
+def beam_step(logits, scores, finished, *, eos_id=-1, fill=0, return_logp=False):
+    """-> (new_scores fp32, parent int32, token int64, new_finished bool), all [B, W]: the module
+    docstring has the definition.  With ``return_logp`` also ``logp`` fp32 [B, W]."""
+    B, W, V = _check_beam_step(logits, scores, finished)
+    if logits.is_cuda:
+        ext = get_ext()  # raises on a GPU without the built extension: no quiet fall-back
+        if ext is not None and logits.dtype in (torch.float32, torch.bfloat16) and B > 0:
+            x = logits if logits.stride(-1) == 1 or V == 1 else logits.contiguous()
+            out = ext.beam_step(x, scores.contiguous(), finished.contiguous(), int(eos_id), int(fill))
+            if out is not None:
+                return tuple(out) if return_logp else tuple(out[:4])
+    return beam_step_ref(logits, scores, finished, eos_id=eos_id, fill=fill, return_logp=return_logp)

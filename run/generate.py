@@ -13,6 +13,11 @@ first ``eos_id``) and ``reference`` (the row's own next ``max_new_tokens`` token
 ``--temperature``, ``--top_k`` and ``--top_p`` shape the draw and ``--seed`` reproduces it.
 ``--noise philox`` draws with ``ops.decode.sample_tokens``: noise keyed by (seed, step, the row's
 index in the split, token id), so a row's draws do not depend on ``--batch_size``.
+
+``--num_beams W`` (W > 1) runs ``GPT2LMModel.beam_search`` instead: ``continuation`` is the best of W
+beams by ``score / length ** length_penalty``, and ``--keep_beams true`` adds ``beams`` (every beam's
+ids, best first) and ``beam_scores`` (their summed log-probabilities).  The search is deterministic:
+it ignores ``--temperature`` and ``--seed`` and excludes ``--top_k``, ``--top_p`` and ``--noise philox``.
 """
 import json
 import os
@@ -70,16 +75,30 @@ def main(namespace):
                 break
             ids = batch["input_ids"].to(dev)
             lens = torch.full((ids.shape[0],), Lp, dtype=torch.int32, device=dev)
-            toks, new_lens = model.generate(ids[:, :Lp].contiguous(), lens, Ln, temperature=args.temperature,
-                                            top_k=args.top_k, top_p=args.top_p, eos_id=eos, generator=gen,
-                                            noise_seed=args.seed if args.noise == "philox" else None, row_base=n)
+            if args.num_beams > 1:
+                beams, beam_lens, beam_scores = model.beam_search(
+                    ids[:, :Lp].contiguous(), lens, Ln, num_beams=args.num_beams, eos_id=eos,
+                    length_penalty=args.length_penalty)
+                beams, beam_lens, beam_scores = beams.cpu(), beam_lens.cpu(), beam_scores.cpu()
+                toks, new_lens = beams[:, 0], beam_lens[:, 0]
+            else:
+                toks, new_lens = model.generate(ids[:, :Lp].contiguous(), lens, Ln, temperature=args.temperature,
+                                                top_k=args.top_k, top_p=args.top_p, eos_id=eos, generator=gen,
+                                                noise_seed=args.seed if args.noise == "philox" else None, row_base=n)
             ids, toks, new_lens = ids.cpu(), toks.cpu(), new_lens.cpu()
+
+            def cut(row, length):
+                cont = row[:int(length)].tolist()
+                return cont[:cont.index(eos)] if eos is not None and eos in cont else cont
+
             for i in range(ids.shape[0]):
-                cont = toks[i, :int(new_lens[i])].tolist()
-                if eos is not None and eos in cont:
-                    cont = cont[:cont.index(eos)]
-                line = {"prompt": ids[i, :Lp].tolist(), "continuation": cont,
+                line = {"prompt": ids[i, :Lp].tolist(), "continuation": cut(toks[i], new_lens[i]),
                         "reference": ids[i, Lp:Lp + Ln].tolist()}
+                if args.num_beams > 1 and args.keep_beams:
+                    # slots that never held a hypothesis (score -inf) are left out
+                    live = [w for w in range(args.num_beams) if beam_scores[i, w] > float("-inf")]
+                    line["beams"] = [cut(beams[i, w], beam_lens[i, w]) for w in live]
+                    line["beam_scores"] = [float(beam_scores[i, w]) for w in live]
                 fout.write(json.dumps(line) + "\n")
             n += ids.shape[0]
     print(f"### wrote {n} continuations to {out_path}")
