@@ -53,6 +53,12 @@ class ContinueSettings(S):
                  "(0 = the raw sum of log-probabilities).")
     keep_beams: bool \
         = _(False, "Beam search: also write 'beams' (every beam's ids, best first) and 'beam_scores'.")
+    lookahead: int \
+        = _(0, "Lookahead decoding with blocks of this many tokens (2 .. 8; 0 = off): greedy decoding's own "
+               "output in fewer model calls. Needs --temperature 0 and excludes --num_beams > 1.")
+    lookup_ngram: int \
+        = _(2, "Lookahead decoding: a row's guesses continue the latest earlier occurrence of its last "
+               "lookup_ngram tokens in its own prompt and output.")
     out_path: str \
         = _("", "Output .jsonl file (default: generated_<checkpoint>_seed<seed>.jsonl next to the checkpoint).")
     precision: Choice("bf16", "fp32") \
@@ -109,6 +115,15 @@ class GenerateSettings(
             if self.num_beams * self.batch_size > 0x7FFFFFFF // max(self.num_heads, 64):
                 raise ValueError(f"--num_beams {self.num_beams} x --batch_size {self.batch_size} cache rows "
                                  "cannot be addressed")
+        if self.lookahead != 0 and not 2 <= self.lookahead <= 8:
+            raise ValueError(f"--lookahead must be 0 (off) or in 2 .. 8, got {self.lookahead}")
+        if self.lookup_ngram < 1:
+            raise ValueError(f"--lookup_ngram must be >= 1, got {self.lookup_ngram}")
+        if self.lookahead:
+            if self.temperature != 0:
+                raise ValueError("--lookahead verifies guesses against the arg-max: it needs --temperature 0")
+            if self.num_beams > 1:
+                raise ValueError("--lookahead excludes --num_beams > 1")
         if self.prompt_len < 1 or self.max_new_tokens < 1:
             raise ValueError("--prompt_len and --max_new_tokens must be >= 1")
         if self.prompt_len + self.max_new_tokens > self.seq_len:

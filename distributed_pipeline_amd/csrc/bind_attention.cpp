@@ -1,5 +1,5 @@
 // Bindings of the attention kernels: training forward / backward (attention.hip,
-// attention128.hip) and the KV-cache decode step (attn_decode.hip).
+// attention128.hip) and the KV-cache decode steps (attn_decode.hip, attn_decode_block.hip).
 #include "bind_util.h"
 
 static std::vector<at::Tensor> attn_fwd(const at::Tensor& qkv, int64_t heads, double p, bool causal,
@@ -150,6 +150,52 @@ static c10::optional<at::Tensor> attn_decode_beam(const at::Tensor& qkv_new, at:
   return attn_decode_any(qkv_new, k_cache, v_cache, lens, n_heads, &src, beams);
 }
 
+// A block of T new tokens per row (csrc/attn_decode_block.hip): qkv_new [B, T, 3 H D] bf16, counts
+// int32 [B] or None (= T) -> out [B, T, H D] bf16: T successive attn_decode calls in one pass over the
+// caches (launchers.h has the definition), or None for a case the kernel does not cover.
+static c10::optional<at::Tensor> attn_decode_block(const at::Tensor& qkv_new, at::Tensor& k_cache, at::Tensor& v_cache,
+                                                   const at::Tensor& lens, int64_t n_heads,
+                                                   c10::optional<at::Tensor> counts) {
+  TORCH_CHECK(qkv_new.dim() == 3 && k_cache.dim() == 4 && v_cache.dim() == 4 && lens.dim() == 1 && n_heads > 0,
+              "attn_decode_block: qkv_new [B, T, 3 H D], caches [B, H, Lmax, D], lens [B]");
+  const int64_t B = k_cache.size(0), H = k_cache.size(1), Lmax = k_cache.size(2), D = k_cache.size(3);
+  const int64_t T = qkv_new.size(1);
+  TORCH_CHECK(H == n_heads && v_cache.sizes() == k_cache.sizes() && qkv_new.size(0) == B &&
+                  qkv_new.size(2) == 3 * H * D && lens.size(0) == B,
+              "attn_decode_block: shapes of qkv_new, the caches, lens and n_heads do not agree");
+  TORCH_CHECK(T >= 1 && T <= 8, "attn_decode_block: T must be in 1 .. 8, got ", T);
+  TORCH_CHECK(lens.scalar_type() == at::kInt, "attn_decode_block: lens must be int32");
+  const bool has_counts = counts.has_value() && counts->defined();
+  if (has_counts)
+    TORCH_CHECK(counts->scalar_type() == at::kInt && counts->dim() == 1 && counts->size(0) == B,
+                "attn_decode_block: counts must be int32 [B]");
+  for (const at::Tensor* t : {&qkv_new, (const at::Tensor*)&k_cache, (const at::Tensor*)&v_cache, &lens})
+    if (!t->is_cuda() || t->device() != qkv_new.device()) return c10::nullopt;
+  if (has_counts && (!counts->is_cuda() || counts->device() != qkv_new.device() || !counts->is_contiguous()))
+    return c10::nullopt;
+  if (qkv_new.scalar_type() != at::kBFloat16 || k_cache.scalar_type() != at::kBFloat16 ||
+      v_cache.scalar_type() != at::kBFloat16)
+    return c10::nullopt;
+  if ((D != 64 && D != 128) || B == 0 || Lmax == 0 || Lmax > 0x7fffffffLL || B * H > 0x7fffffffLL) return c10::nullopt;
+  auto rows_ok = [&](const at::Tensor& c) {  // packed rows of D; 16-byte row starts
+    return c.stride(3) == 1 && c.stride(2) == D && c.stride(0) % 8 == 0 && c.stride(1) % 8 == 0 &&
+           reinterpret_cast<uintptr_t>(c.data_ptr()) % 16 == 0;
+  };
+  if (!rows_ok(k_cache) || !rows_ok(v_cache) || !lens.is_contiguous()) return c10::nullopt;
+  if (qkv_new.stride(2) != 1 || qkv_new.stride(0) % 8 != 0 || qkv_new.stride(1) % 8 != 0 ||
+      reinterpret_cast<uintptr_t>(qkv_new.data_ptr()) % 16 != 0)
+    return c10::nullopt;
+  const c10::DeviceGuard guard(qkv_new.device());
+  at::Tensor out = at::empty({B, T, H * D}, qkv_new.options());
+  const bool ok = dpa::launch_attn_decode_block(
+      bf_ptr(qkv_new), qkv_new.stride(0), qkv_new.stride(1), bf_mut(k_cache), bf_mut(v_cache), k_cache.stride(0),
+      k_cache.stride(1), v_cache.stride(0), v_cache.stride(1), lens.data_ptr<int>(),
+      has_counts ? counts->data_ptr<int>() : nullptr, (int)B, (int)T, (int)H, (int)Lmax, (int)D, bf_mut(out),
+      cur_stream());
+  if (!ok) return c10::nullopt;
+  return out;
+}
+
 void dpa::register_attention(pybind11::module& m) {
   m.def("attn128_supports", &dpa::attn128_supports, "the persistent L = 128 attention covers (L, D, causal)");
   m.def("attn_fwd", &attn_fwd, "fused attention forward (head_dim 64/128) -> (out, lse)", py::arg("qkv"),
@@ -170,4 +216,8 @@ void dpa::register_attention(pybind11::module& m) {
         "attn_decode through a cache indirection table: rows in groups of `beams`, src uint8 [R, Lmax] names the group slot holding each cached key -> out [R, H D] bf16 | None (case not covered)",
         py::arg("qkv_new"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"), py::arg("n_heads"),
         py::arg("src"), py::arg("beams"));
+  m.def("attn_decode_block", &attn_decode_block,
+        "KV-cache append + attention of a block of T <= 8 new tokens per row, as T successive attn_decode calls in one pass over the caches -> out [B, T, H D] bf16 | None (case not covered)",
+        py::arg("qkv_new"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"), py::arg("n_heads"),
+        py::arg("counts") = py::none());
 }

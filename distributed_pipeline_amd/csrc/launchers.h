@@ -233,6 +233,21 @@ bool launch_attn_decode_beam(const uint16_t* qkv_new, int64_t qkv_stride, uint16
                              const uint8_t* src, int64_t src_stride, int W, int B, int H, int Lmax, int D,
                              uint16_t* out, hipStream_t s);
 
+// ---- attn_decode_block.hip: the same step for a block of T new tokens per row (lookahead decoding) ----
+// qkv_new [B][T][3][H][D] bf16 (row b, token j at b * qkv_sb + j * qkv_st elements), counts [B] int32
+// or null (= T), out [B][T][H][D] bf16.  With c_b = 0 for lens[b] outside [0, Lmax) and otherwise
+// clamp(counts[b], 0, min(T, Lmax - lens[b])), the call equals T launch_attn_decode calls, call j on
+// token j with lens[b] + j where j < c_b and -1 elsewhere - bit for bit, each query keeping the plain
+// kernel's fold order: tokens j < c_b are stored at cache rows lens[b] + j and attend over the keys
+// 0 .. lens[b] + j, queries j >= c_b store nothing and return zeros, cache rows at or beyond
+// lens[b] + c_b are neither read nor written, lens and counts are not modified.  T == 1 without
+// counts is launch_attn_decode itself.  false, with no launch: as launch_attn_decode, or T outside
+// 1 .. 8, or qkv_st no multiple of 8.
+bool launch_attn_decode_block(const uint16_t* qkv_new, int64_t qkv_sb, int64_t qkv_st, uint16_t* k_cache,
+                              uint16_t* v_cache, int64_t k_sb, int64_t k_sh, int64_t v_sb, int64_t v_sh,
+                              const int* lens, const int* counts, int B, int T, int H, int Lmax, int D,
+                              uint16_t* out, hipStream_t s);
+
 // ---- beam_step.hip: log-softmax + score + top-W of W V candidates (beam search) ----------
 // logits [B][W][V] fp32 or bf16 (element strides stride_b, stride_w >= 0 - 0 repeats a row - and 1),
 // scores fp32 [B][W], finished bytes [B][W] -> the first W candidates of each b in the order

@@ -189,6 +189,132 @@ class GPT2LMModel(nn.Module):
         return out, new_lens
 
     @torch.no_grad()
+    def decode_block(self, tokens, cache, counts=None):
+        """T tokens per row, token j of row b at position ``cache.lens[b] + j`` -> logits [B, T, V],
+        the logits at j saying what follows token j.  ``counts`` (int [B], default T): how many of a
+        row's tokens are real - ``ops.decode.attention_decode_block`` has the exact rule; the logits of
+        the others mean nothing and their keys are not stored.  ``cache.lens`` is NOT advanced: the
+        caller commits as many positions as it accepted, and what was stored beyond them is
+        overwritten or never read."""
+        from ..ops.decode import attention_decode_block
+        dt = self.compute_dtype
+        B, T = tokens.shape
+        heads = cache.heads
+        pos = cache.lens.long().view(B, 1) + torch.arange(T, device=tokens.device).view(1, T)
+        pos = pos.clamp(0, self.cfg["max_position_embeddings"] - 1).view(-1)
+        if counts is not None:
+            counts = counts.to(torch.int32)
+        # the B T tokens stand where decode_step has its B rows: the same kernels around the attention
+        ln0 = self.h[0].ln_1
+        x, a = ops.residual_layernorm(self.wte(tokens.reshape(1, B * T), dt), None, ln0.weight, ln0.bias, 0.0,
+                                      ln0.eps, False, pos=self.wpe(pos, dt))
+
+        def attend(i, qkv):
+            return attention_decode_block(qkv.view(B, T, -1), cache.k[i], cache.v[i], cache.lens, heads,
+                                          counts=counts).view(1, B * T, -1)
+
+        a = self._blocks(x, a, attend)
+        return ops.linear(a.view(B * T, -1), self.wte.weight).view(B, T, -1)
+
+    @torch.no_grad()
+    def generate_lookahead(self, input_ids, lens, max_new_tokens, *, lookahead, ngram=2, eos_id=None, cache=None,
+                           check_every=4, draft=None, return_stats=False):
+        """Greedy continuation by lookahead decoding -> (tokens [B, max_new_tokens], new_lens [B]),
+        with the meanings of :meth:`generate`: its ``temperature=0`` result wherever every arg-max on
+        the way is the same in both, in fewer model calls.
+
+        One iteration runs ``T = lookahead`` tokens per row through :meth:`decode_block`: the row's
+        last committed token and T - 1 guesses, by default copied from the row's own history
+        (``ops.decode.lookup_draft`` with ``ngram``).  The logits at block position j say what follows
+        token j, so the longest prefix of guesses that equal the arg-max in front of them is accepted
+        and the arg-max behind it comes free: a row emits 1 .. T tokens per call, cut behind the first
+        ``eos_id``.  A row's block is cut to what its cache and ``max_new_tokens`` leave room for.
+        Keys stored for rejected guesses lie at or beyond ``cache.lens`` and are overwritten or never
+        read.  Rows finish and are parked as in :meth:`generate` (a row that used up
+        ``max_new_tokens`` has not run its last token); there are at most ``max_new_tokens - 1``
+        iterations, all on the device, and the host looks once every ``check_every`` iterations (0:
+        never) to stop when every row has finished.
+
+        ``draft``: a callable with ``lookup_draft``'s signature ``(history [B, Lh], n [B], *, ngram,
+        max_draft) -> (draft [B, max_draft], k [B])`` to use instead - ``history[b, :n[b]]`` is the
+        row's prompt and output so far.  ``return_stats`` adds a dict: ``model_calls`` (iterations with
+        a live row), ``proposed`` and ``accepted`` guesses, read back once at the end."""
+        from utils.lm_sampling import greedy
+        from ..ops.decode import lookup_draft
+        T, g, N = int(lookahead), int(ngram), int(max_new_tokens)
+        if not 2 <= T <= 8:
+            raise ValueError(f"lookahead must be in 2 .. 8, got {lookahead}")
+        if g < 1:
+            raise ValueError(f"ngram must be >= 1, got {ngram}")
+        draft = lookup_draft if draft is None else draft
+        B, Lp = input_ids.shape
+        dev = input_ids.device
+        if cache is None:
+            cache = self.init_cache(B, min(Lp + N, self.cfg["max_position_embeddings"]), dev)
+        max_len = cache.max_len
+        fill = 0 if eos_id is None else int(eos_id)
+        # T spare columns behind both: where the masked-out slots of a block are written
+        out = torch.full((B, N + T), fill, dtype=torch.long, device=dev)
+        Lh = Lp + N
+        hist = torch.zeros(B, Lh + T, dtype=torch.long, device=dev)
+        n = lens.to(device=dev, dtype=torch.long).clone()  # tokens of the row's history
+        hist[:, :Lp] = torch.where(torch.arange(Lp, device=dev).view(1, Lp) < n.view(B, 1), input_ids, 0)
+        new_lens = torch.zeros(B, dtype=torch.long, device=dev)
+        done = torch.zeros(B, dtype=torch.bool, device=dev)
+        stats = torch.zeros(3, dtype=torch.long, device=dev)  # model calls, proposed, accepted
+        logits = self.prefill(input_ids, lens, cache)
+        if N == 0:
+            res = (out[:, :0], new_lens)
+            return res + ({"model_calls": 0, "proposed": 0, "accepted": 0},) if return_stats else res
+        last = greedy(logits)
+        out[:, 0] = last
+        hist.scatter_(1, n.view(B, 1), last.view(B, 1))
+        n += 1
+        new_lens += 1
+        if eos_id is not None:
+            done = done | (last == fill)
+        pos = cache.lens.clone()  # a row's cached tokens, while cache.lens parks the rows with nothing to run
+        done = done | (pos >= max_len)
+        idle = done | (new_lens >= N)
+        cols = torch.arange(T, device=dev).view(1, T)
+        for it in range(N - 1):
+            cache.lens.copy_(torch.where(idle, -1, pos))
+            if check_every and it and it % check_every == 0 and bool(idle.all()):
+                break
+            guess, k = draft(hist[:, :Lh], n, ngram=g, max_draft=T - 1)
+            counts = torch.minimum(torch.minimum(1 + k.long(), max_len - pos.long()), N - new_lens)
+            counts = torch.where(idle, 0, counts).clamp(min=0)
+            block = torch.cat([last.view(B, 1), guess], 1)
+            logits = self.decode_block(block, cache, counts)
+            picks = greedy(logits.view(B * T, -1)).view(B, T)
+            # a: the guesses accepted - the longest prefix with block[j + 1] == picks[j], j + 1 < counts
+            match = (block[:, 1:] == picks[:, :-1]) & (cols[:, 1:] < counts.view(B, 1))
+            a = match.long().cumprod(1).sum(1)
+            keep = (cols <= a.view(B, 1)) & ~idle.view(B, 1)
+            if eos_id is not None:  # nothing behind the first eos_id
+                is_eos = keep & (picks == fill)
+                keep = keep & (is_eos.long().cumsum(1) - is_eos.long() == 0)
+            e = keep.long().sum(1)  # tokens emitted: 1 .. a + 1 for a live row
+            out.scatter_(1, torch.where(keep, new_lens.view(B, 1) + cols, N + cols), picks)
+            hist.scatter_(1, torch.where(keep, n.view(B, 1) + cols, Lh + cols), picks)
+            last = torch.where(idle, last, picks.gather(1, (e - 1).clamp(min=0).view(B, 1)).view(B))
+            stats += torch.stack([(~idle).any().long(), (counts - 1).clamp(min=0).sum(),
+                                  torch.where(idle, 0, a).sum()])
+            new_lens += e
+            n += e
+            pos += e.to(pos.dtype)
+            if eos_id is not None:
+                done = done | (keep & (picks == fill)).any(1)
+            done = done | (pos >= max_len)  # no room to run the last token emitted
+            idle = done | (new_lens >= N)
+        cache.lens.copy_(torch.where(done, -1, pos))
+        res = (out[:, :N].contiguous(), new_lens)
+        if return_stats:
+            calls, proposed, accepted = stats.tolist()
+            res += ({"model_calls": calls, "proposed": proposed, "accepted": accepted},)
+        return res
+
+    @torch.no_grad()
     def beam_search(self, input_ids, lens, max_new_tokens, *, num_beams, eos_id=None, length_penalty=0.0,
                     cache=None, check_every=16):
         """Continue right-padded prompts with beam search -> (tokens [B, W, max_new_tokens], new_lens

@@ -1,6 +1,7 @@
 """
 The per-token ops of GPT-2 generation: single-query attention over a K/V cache (directly, or through
-the indirection table of a beam search), one beam-search step, and the choice of the next token.
+the indirection table of a beam search), the same for a block of new tokens with the guesses that
+fill it (lookahead decoding), one beam-search step, and the choice of the next token.
 
 Attention of one decode step
 ----------------------------
@@ -34,6 +35,42 @@ call's bit for bit.  Caller's contract: no active row may read a (slot, position
 row of the same call appends to; this holds whenever the active rows of a group have equal ``lens``,
 which is what beam search guarantees.  Re-parenting W hypotheses then rewrites ``W Lmax`` bytes per
 prompt instead of gathering ``[layers, 2, B W, H, Lmax, D]`` into a second buffer.
+
+Attention of a block of new tokens: ``attention_decode_block``
+--------------------------------------------------------------
+``attention_decode_block(qkv_new [B, T, 3*H*D], k_cache, v_cache, lens int32 [B], n_heads, *,
+counts=None) -> out [B, T, H*D]`` with ``1 <= T <= 8``: T new tokens per row against the cache in one
+pass over K and V (lookahead decoding: a committed token and T - 1 guessed ones).
+
+* Let ``c_b = 0`` for an inactive row (``lens[b]`` outside ``[0, Lmax)``), and otherwise
+  ``c_b = clamp(counts[b], 0, min(T, Lmax - lens[b]))``; ``counts=None`` means T.
+* The call equals T successive ``attention_decode`` calls: call j runs on ``qkv_new[:, j]`` with
+  ``lens_j[b] = lens[b] + j`` if ``j < c_b``, else -1.
+* So query ``j < c_b`` stores its k and v at cache row ``lens[b] + j``, the bits of ``qkv_new``, and
+  attends over the keys ``0 .. lens[b] + j``, rounded once to bf16.
+* Query ``j >= c_b`` stores nothing and returns zeros.
+* ``lens`` and ``counts`` are not modified; the caller commits as many positions as it accepts.
+* Cache rows at or beyond ``lens[b] + c_b`` are neither read nor written, whatever they hold.
+
+bf16 on a HIP device with D in {64, 128}: one kernel (csrc/attn_decode_block.hip) that keeps the
+plain kernel's fold order per query - a key goes to the (wave, lane group, iteration) its position
+gives it there, the query's own key is folded last, the keys of the block in front of a query are
+taken from ``qkv_new`` - so output and caches are meant to equal those of the T sequential calls bit
+for bit; ``T = 1`` without ``counts`` is the plain kernel itself.  Anything else:
+:func:`attention_decode_block_ref`, the T masked ``attention_decode_ref`` calls as written.  There is
+no table (beam) variant.
+
+The guesses: ``lookup_draft``
+-----------------------------
+``lookup_draft(history int64 [B, Lh], n [B], *, ngram, max_draft) -> (draft int64 [B, max_draft],
+k int64 [B])`` copies a row's guesses from its own history ("prompt lookup").  For row b let s be the
+first ``n_b`` tokens (``n_b`` clamped to ``[0, Lh]``) and ``g = ngram``.  If there is an
+``i <= n_b - g - 1`` with ``s[i : i+g] == s[n_b-g : n_b]``, take the largest such i; with
+``p = n_b - g - i >= 1`` the row gets ``k = max_draft`` and ``draft[m] = s[i + g + (m mod p)]`` - a copy
+that may run into its own output, as an LZ77 match does, so a row that repeats with period p is
+continued with that period.  Otherwise ``k = 0`` and the draft row is zeros.  Tensor ops only, on either
+device (an ``unfold`` compare, a masked maximum over the start index, a gather): no kernel, no host
+synchronisation, integers only.
 
 One beam-search step: ``beam_step``
 -----------------------------------
@@ -182,6 +219,82 @@ def attention_decode(qkv_new, k_cache, v_cache, lens, n_heads, *, src=None, beam
             if out is not None:
                 return out
     return attention_decode_ref(qkv_new, k_cache, v_cache, lens, n_heads, src=src, beams=beams)
+
+
+# ---- attention_decode_block, lookup_draft (lookahead decoding) -----------------------------------
+
+BLOCK_MAX = 8  # the largest block of csrc/attn_decode_block.hip
+
+
+def _check_block(qkv_new, k_cache, lens, n_heads, counts):
+    if qkv_new.dim() != 3 or k_cache.dim() != 4:
+        raise ValueError(f"qkv_new must be [B, T, 3*H*D] and the caches [B, H, Lmax, D], got "
+                         f"{tuple(qkv_new.shape)}, {tuple(k_cache.shape)}")
+    B, H, _, D = k_cache.shape
+    T = qkv_new.shape[1]
+    if not 1 <= T <= BLOCK_MAX:
+        raise ValueError(f"a block holds 1 .. {BLOCK_MAX} tokens, got T = {T}")
+    if H != n_heads or tuple(qkv_new.shape) != (B, T, 3 * H * D) or tuple(lens.shape) != (B,):
+        raise ValueError("shapes of qkv_new, the caches, lens and n_heads do not agree")
+    if counts is not None and (counts.dtype != torch.int32 or tuple(counts.shape) != (B,)):
+        raise ValueError(f"counts must be int32 [{B}], got {counts.dtype} {tuple(counts.shape)}")
+    return B, T
+
+
+def attention_decode_block_ref(qkv_new, k_cache, v_cache, lens, n_heads, *, counts=None):
+    """The definition as written (any device, any dtype): T ``attention_decode_ref`` calls, call j
+    with ``lens + j`` for the rows with ``j < c_b`` and -1 for the others."""
+    B, T = _check_block(qkv_new, k_cache, lens, n_heads, counts)
+    Lmax = k_cache.shape[2]
+    n = lens.long()
+    c = torch.full_like(n, T) if counts is None else counts.to(n.device).long()
+    c = torch.where((n >= 0) & (n < Lmax), torch.minimum(c.clamp(0, T), Lmax - n), 0)
+    outs = [attention_decode_ref(qkv_new[:, j], k_cache, v_cache, torch.where(j < c, n + j, -1).to(torch.int32),
+                                 n_heads) for j in range(T)]
+    return torch.stack(outs, 1)
+
+
+@torch.no_grad()
+def attention_decode_block(qkv_new, k_cache, v_cache, lens, n_heads, *, counts=None):
+    """-> out [B, T, H*D] in ``qkv_new``'s dtype; ``k_cache`` / ``v_cache`` updated in place.  The
+    module docstring has the definition."""
+    _check_block(qkv_new, k_cache, lens, n_heads, counts)
+    if qkv_new.is_cuda:
+        ext = get_ext()  # raises on a GPU without the built extension: no quiet fall-back
+        if ext is not None:
+            if (qkv_new.stride(-1) != 1 or qkv_new.stride(0) % 8 or qkv_new.stride(1) % 8
+                    or qkv_new.data_ptr() % 16):
+                qkv_new = qkv_new.contiguous()
+            out = ext.attn_decode_block(qkv_new, k_cache, v_cache, lens, int(n_heads),
+                                        None if counts is None else counts.contiguous())
+            if out is not None:
+                return out
+    return attention_decode_block_ref(qkv_new, k_cache, v_cache, lens, n_heads, counts=counts)
+
+
+@torch.no_grad()
+def lookup_draft(history, n, *, ngram, max_draft):
+    """-> (draft int64 [B, max_draft], k int64 [B]): the module docstring has the definition."""
+    g, M = int(ngram), int(max_draft)
+    if g < 1 or M < 0:
+        raise ValueError(f"ngram must be >= 1 and max_draft >= 0, got {ngram}, {max_draft}")
+    B, Lh = history.shape
+    dev = history.device
+    n = n.to(device=dev, dtype=torch.long).clamp(0, Lh)
+    if Lh < g + 1 or M == 0:
+        return torch.zeros(B, M, dtype=torch.long, device=dev), torch.zeros(B, dtype=torch.long, device=dev)
+    win = history.unfold(1, g, 1)  # [B, Lh - g + 1, g]: window i is s[i : i + g]
+    nw = Lh - g + 1
+    rows = torch.arange(B, device=dev)
+    suffix = win[rows, (n - g).clamp(0, nw - 1)]  # s[n - g : n] where n >= g
+    start = torch.arange(nw, device=dev).view(1, nw)
+    hit = (win == suffix.unsqueeze(1)).all(-1) & (start <= (n - g - 1).view(B, 1))
+    i = torch.where(hit, start, -1).amax(1)  # the latest earlier occurrence, -1: none
+    found = i >= 0
+    p = (n - g - i).clamp(min=1)
+    at = i.view(B, 1) + g + torch.arange(M, device=dev).view(1, M) % p.view(B, 1)
+    draft = torch.where(found.view(B, 1), history.gather(1, at.clamp(0, Lh - 1)), 0)
+    return draft, torch.where(found, M, 0)
 
 
 # ---- sample_tokens ------------------------------------------------------------------------------

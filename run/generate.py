@@ -18,6 +18,11 @@ index in the split, token id), so a row's draws do not depend on ``--batch_size`
 beams by ``score / length ** length_penalty``, and ``--keep_beams true`` adds ``beams`` (every beam's
 ids, best first) and ``beam_scores`` (their summed log-probabilities).  The search is deterministic:
 it ignores ``--temperature`` and ``--seed`` and excludes ``--top_k``, ``--top_p`` and ``--noise philox``.
+
+``--lookahead T`` (2 .. 8, with ``--temperature 0``) runs ``GPT2LMModel.generate_lookahead``: greedy
+decoding's own output, T tokens per model call - the last one and T - 1 guesses copied from behind the
+latest earlier occurrence of the row's last ``--lookup_ngram`` tokens - of which the verified prefix is
+kept.  The run prints the model calls it made and how many guesses were accepted.
 """
 import json
 import os
@@ -69,6 +74,7 @@ def main(namespace):
     eos = None if args.eos_id < 0 else args.eos_id
     Lp, Ln = args.prompt_len, args.max_new_tokens
     n = 0
+    look = {"model_calls": 0, "tokens": 0, "proposed": 0, "accepted": 0}
     with open(out_path, "w") as fout:
         for b, batch in enumerate(data):
             if b >= args.num_batches:
@@ -81,6 +87,13 @@ def main(namespace):
                     length_penalty=args.length_penalty)
                 beams, beam_lens, beam_scores = beams.cpu(), beam_lens.cpu(), beam_scores.cpu()
                 toks, new_lens = beams[:, 0], beam_lens[:, 0]
+            elif args.lookahead:
+                toks, new_lens, stats = model.generate_lookahead(
+                    ids[:, :Lp].contiguous(), lens, Ln, lookahead=args.lookahead, ngram=args.lookup_ngram,
+                    eos_id=eos, return_stats=True)
+                for key, val in stats.items():
+                    look[key] += val
+                look["tokens"] += int(new_lens.sum())
             else:
                 toks, new_lens = model.generate(ids[:, :Lp].contiguous(), lens, Ln, temperature=args.temperature,
                                                 top_k=args.top_k, top_p=args.top_p, eos_id=eos, generator=gen,
@@ -101,6 +114,9 @@ def main(namespace):
                     line["beam_scores"] = [float(beam_scores[i, w]) for w in live]
                 fout.write(json.dumps(line) + "\n")
             n += ids.shape[0]
+    if args.lookahead:
+        print(f"### lookahead {args.lookahead}: {look['model_calls']} model calls for {look['tokens']} tokens, "
+              f"{look['accepted']} of {look['proposed']} guesses accepted")
     print(f"### wrote {n} continuations to {out_path}")
     return out_path
 
