@@ -59,6 +59,20 @@ class ContinueSettings(S):
     lookup_ngram: int \
         = _(2, "Lookahead decoding: a row's guesses continue the latest earlier occurrence of its last "
                "lookup_ngram tokens in its own prompt and output.")
+    repetition_penalty: float \
+        = _(1.0, "Logits of the ids a row already holds are divided by this if positive and multiplied by it if "
+                 "negative (> 1 discourages repeats); 1 = off.")
+    presence_penalty: float \
+        = _(0.0, "Subtracted once from the logit of every id a row already holds; 0 = off.")
+    frequency_penalty: float \
+        = _(0.0, "Subtracted from the logit of an id once per occurrence in the row so far; 0 = off.")
+    no_repeat_ngram: int \
+        = _(0, "Ban every token that would complete an n-gram of this size the row already holds; 0 = off.")
+    min_new_tokens: int \
+        = _(0, "eos_id cannot be chosen before this many tokens were generated; needs --eos_id.")
+    penalize_prompt: bool \
+        = _(True, "The penalties and the n-gram ban see the prompt as well as the tokens generated so far; "
+                  "false: the generated tokens alone.")
     out_path: str \
         = _("", "Output .jsonl file (default: generated_<checkpoint>_seed<seed>.jsonl next to the checkpoint).")
     precision: Choice("bf16", "fp32") \
@@ -90,6 +104,12 @@ class GenerateSettings(
 
     # the JSON loading and train-only key filtering of run.sample's settings, on this class's fields
     from_argparse = classmethod(SampleSettings.from_argparse.__func__)
+
+    def logit_processors(self):
+        """The keywords ``GPT2LMModel.generate`` and ``beam_search`` take for the logit processors."""
+        return dict(repetition_penalty=self.repetition_penalty, presence_penalty=self.presence_penalty,
+                    frequency_penalty=self.frequency_penalty, no_repeat_ngram=self.no_repeat_ngram,
+                    min_new_tokens=self.min_new_tokens, penalize_prompt=self.penalize_prompt)
 
     def check(self):
         """Reject what no checkpoint could make sense of (before one is read)."""
@@ -124,6 +144,21 @@ class GenerateSettings(
                 raise ValueError("--lookahead verifies guesses against the arg-max: it needs --temperature 0")
             if self.num_beams > 1:
                 raise ValueError("--lookahead excludes --num_beams > 1")
+        if not self.repetition_penalty > 0:
+            raise ValueError(f"--repetition_penalty must be > 0, got {self.repetition_penalty}")
+        if self.no_repeat_ngram < 0:
+            raise ValueError(f"--no_repeat_ngram must be >= 0, got {self.no_repeat_ngram}")
+        if not 0 <= self.min_new_tokens <= self.max_new_tokens:
+            raise ValueError(f"--min_new_tokens must be in 0 .. --max_new_tokens {self.max_new_tokens}, got "
+                             f"{self.min_new_tokens}")
+        if self.min_new_tokens > 0 and self.eos_id < 0:
+            raise ValueError("--min_new_tokens holds off eos_id: it needs --eos_id")
+        if self.lookahead and self.logit_processors() != dict(
+                repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, no_repeat_ngram=0,
+                min_new_tokens=0, penalize_prompt=True):
+            raise ValueError("--lookahead excludes --repetition_penalty, --presence_penalty, --frequency_penalty, "
+                             "--no_repeat_ngram, --min_new_tokens and --penalize_prompt: its guesses continue "
+                             "repeated n-grams")
         if self.prompt_len < 1 or self.max_new_tokens < 1:
             raise ValueError("--prompt_len and --max_new_tokens must be >= 1")
         if self.prompt_len + self.max_new_tokens > self.seq_len:

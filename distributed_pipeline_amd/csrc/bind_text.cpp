@@ -1,5 +1,5 @@
 // Bindings of the generation and text-metric kernels: token sampling (sample.hip), the beam-search
-// step (beam_step.hip) and the
+// step (beam_step.hip), the logit processors (logit_penalty.hip) and the
 // per-group n-gram / LCS counts (ngram_match.hip, ngram_distinct.hip, lcs.hip).
 #include <limits.h>
 
@@ -87,6 +87,36 @@ static c10::optional<std::vector<at::Tensor>> beam_step(const at::Tensor& logits
   return out;
 }
 
+// The logit processors of generation, in place (csrc/logit_penalty.hip; the definition is in ops/decode.py):
+// logits [R, V] fp32 or bf16 (last stride 1, rows that do not overlap), hist [R, Lh] int32 or int64 (any
+// strides), n and start (optional) int32 [R] -> true when the kernel ran, false for a case it does not
+// cover (CPU tensor, dtype, Lh > 2048, a last stride other than 1, n or start not contiguous int32).
+static bool penalize_logits(at::Tensor& logits, const at::Tensor& hist, const at::Tensor& n,
+                            const c10::optional<at::Tensor>& start, double theta, double alpha_p, double alpha_f,
+                            int64_t ngram) {
+  TORCH_CHECK(logits.dim() == 2 && hist.dim() == 2 && n.dim() == 1, "penalize_logits: logits [R, V], hist [R, Lh], n [R]");
+  const int64_t R = logits.size(0), V = logits.size(1), Lh = hist.size(1);
+  TORCH_CHECK(hist.size(0) == R && n.size(0) == R, "penalize_logits: hist and n must have logits' R rows");
+  TORCH_CHECK(!has(start) || (start->dim() == 1 && start->size(0) == R), "penalize_logits: start must be [R]");
+  TORCH_CHECK(theta > 0 && ngram >= 0, "penalize_logits: repetition_penalty must be > 0 and no_repeat_ngram >= 0");
+  TORCH_CHECK(R <= 1 || logits.stride(0) >= V, "penalize_logits: the rows of logits overlap");
+  if (R == 0 || V == 0 || Lh == 0) return true;
+  if (!logits.is_cuda() || (logits.scalar_type() != at::kFloat && logits.scalar_type() != at::kBFloat16))
+    return false;
+  if (hist.scalar_type() != at::kInt && hist.scalar_type() != at::kLong) return false;
+  auto i32 = [&](const at::Tensor& t) {
+    return t.scalar_type() == at::kInt && t.is_contiguous() && t.device() == logits.device();
+  };
+  if (hist.device() != logits.device() || !i32(n) || (has(start) && !i32(*start))) return false;
+  if (R > 0x7fffffffLL || V > 0x7fffffffLL || Lh > dpa::LP_MAX_L || (V > 1 && logits.stride(1) != 1)) return false;
+  const c10::DeviceGuard guard(logits.device());
+  return dpa::launch_logit_penalty(logits.data_ptr(), logits.scalar_type() == at::kBFloat16, logits.stride(0), R,
+                                   (int)V, hist.data_ptr(), hist.scalar_type() == at::kLong, hist.stride(0),
+                                   hist.stride(1), (int)Lh, n.data_ptr<int>(),
+                                   has(start) ? start->data_ptr<int>() : nullptr, (float)theta, (float)alpha_p,
+                                   (float)alpha_f, (int)std::min<int64_t>(ngram, INT_MAX), cur_stream());
+}
+
 // ---- per-group token ops: tokens [G, K, L] int32 / int64, lens [G, K] int32 -> int32 counts ----
 static void check_token_group(const at::Tensor& tokens, const at::Tensor& lens, const char* op) {
   CHECK_DEV(tokens); CHECK_CONTIG(tokens); CHECK_DEV(lens); CHECK_CONTIG(lens);
@@ -148,6 +178,10 @@ void dpa::register_text(pybind11::module& m) {
   m.def("beam_step", &beam_step,
         "one beam-search step: log-softmax + cumulative score + the W best of W V candidates -> [new_scores, parent, token, new_finished, logp] | None (case not covered)",
         py::arg("logits"), py::arg("scores"), py::arg("finished"), py::arg("eos_id") = -1, py::arg("fill") = 0);
+  m.def("penalize_logits", &penalize_logits,
+        "repetition / presence / frequency penalty and no-repeat-n-gram ban on logits, in place -> True | False (case not covered)",
+        py::arg("logits"), py::arg("hist"), py::arg("n"), py::arg("start"), py::arg("theta"), py::arg("alpha_p"),
+        py::arg("alpha_f"), py::arg("ngram"));
   m.def("ngram_matches", &ngram_matches,
         "clipped 1..4-gram match counts of every sequence pair of a group -> int32 [G, K, K, 4] | None (shape not covered)",
         py::arg("tokens"), py::arg("lens"));

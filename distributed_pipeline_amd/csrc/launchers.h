@@ -279,6 +279,20 @@ bool launch_sample_tokens(const void* logits, bool bf16, int64_t row_stride, int
 bool launch_sample_uniforms(float* out, int64_t B, int V, uint64_t seed, uint32_t step, uint64_t row_base,
                             hipStream_t st);
 
+// ---- logit_penalty.hip: repetition / presence / frequency penalty and n-gram ban, in place ----
+// For every row r of logits ([R][V] fp32 or bf16, rows row_stride elements apart and not overlapping, any
+// alignment) with n[r] >= 0: the window is hist[r][lo .. hi), hi = min(n[r], Lh), lo = clamp(start[r], 0,
+// Lh) (0 with start == nullptr); hist holds int32 or int64 ids, element strides hs_r and hs_l.  Each
+// distinct id x of the window inside [0, V), seen c times, is updated once: s = logit, s = s < 0 ? s theta
+// : s / theta, s = s - (alpha_p + alpha_f c), each step one fp32 rounding, and s = -inf when x would
+// complete a g-gram that the window already holds (g >= 1).  Nothing else is written and nothing beyond
+// hi is read.  One launch, one workgroup per row, no workspace, no atomics.  false, with no launch: Lh
+// outside 1 .. LP_MAX_L, R outside 1 .. 2^31 - 1, V < 1, theta not > 0, g < 0, or a null pointer.
+constexpr int LP_MAX_L = 2048;
+bool launch_logit_penalty(void* logits, bool bf16, int64_t row_stride, int64_t R, int V, const void* hist,
+                          bool hist64, int64_t hs_r, int64_t hs_l, int Lh, const int* n, const int* start,
+                          float theta, float alpha_p, float alpha_f, int g, hipStream_t st);
+
 // ---- ngram_match.hip: clipped n-gram match counts of sequence pairs (MBR, BLEU) --------
 // m[g][i][j][n-1] = sum over the distinct n-grams y of min(count_i(y), count_j(y)), n = 1..4, for the
 // K sequences tokens[g][k][0 .. lens[g][k]) of every group (ids there in [0, 2^31); lens clamped to

@@ -13,6 +13,26 @@ from . import presets
 from .layers import Embedding, GPT2Block, LayerNorm
 
 
+def _logit_processors(repetition_penalty, presence_penalty, frequency_penalty, no_repeat_ngram, min_new_tokens,
+                      eos_id):
+    """-> (the scalar keywords of ``ops.decode.penalize_logits_``, or None with all four at their
+    defaults; ``min_new_tokens`` as an int), checked."""
+    kw = dict(repetition_penalty=float(repetition_penalty), presence_penalty=float(presence_penalty),
+              frequency_penalty=float(frequency_penalty), no_repeat_ngram=int(no_repeat_ngram))
+    if not kw["repetition_penalty"] > 0:
+        raise ValueError(f"repetition_penalty must be > 0, got {repetition_penalty}")
+    if kw["no_repeat_ngram"] < 0:
+        raise ValueError(f"no_repeat_ngram must be >= 0, got {no_repeat_ngram}")
+    M = int(min_new_tokens)
+    if M < 0:
+        raise ValueError(f"min_new_tokens must be >= 0, got {min_new_tokens}")
+    if M > 0 and eos_id is None:
+        raise ValueError("min_new_tokens holds off eos_id: it needs one")
+    if kw == dict(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, no_repeat_ngram=0):
+        kw = None
+    return kw, M
+
+
 class GPT2LMModel(nn.Module):
     def __init__(self, *, config_name="gpt2", vocab_size=0, seq_len=1024, hidden_size=0,
                  num_layers=0, num_heads=0, dropout=0.1, compute_dtype=torch.bfloat16, **_):
@@ -141,7 +161,9 @@ class GPT2LMModel(nn.Module):
 
     @torch.no_grad()
     def generate(self, input_ids, lens, max_new_tokens, *, temperature=1.0, top_k=0, top_p=0.0, eos_id=None,
-                 generator=None, cache=None, check_every=16, noise_seed=None, row_base=0):
+                 generator=None, cache=None, check_every=16, noise_seed=None, row_base=0, repetition_penalty=1.0,
+                 presence_penalty=0.0, frequency_penalty=0.0, no_repeat_ngram=0, min_new_tokens=0,
+                 penalize_prompt=True):
         """Continue right-padded prompts -> (tokens [B, max_new_tokens], new_lens [B]).
 
         ``temperature == 0`` is greedy (ties to the lowest id); otherwise ``logits / temperature``,
@@ -154,9 +176,19 @@ class GPT2LMModel(nn.Module):
         ``new_lens[b]`` counts the tokens the row really produced, a closing ``eos_id`` included.
         ``cache``: one from :meth:`init_cache` to use (default: a new one of just the size needed).
         The loop runs on the device; the host looks at it once every ``check_every`` steps (0:
-        never), to stop early when every row has finished."""
+        never), to stop early when every row has finished.
+
+        Logit processors.  With any of ``repetition_penalty``, ``presence_penalty``,
+        ``frequency_penalty`` and ``no_repeat_ngram`` off its default, the loop keeps each row's
+        prompt and output so far on the device and every step's logits, the prefill's included, go
+        through ``ops.decode.penalize_logits_`` before the token is chosen; ``penalize_prompt=False``
+        leaves the prompt out of the window (``start = lens``).  ``min_new_tokens = M`` sets the
+        ``eos_id`` logit of a row that has produced fewer than M tokens to -inf first.  With all at
+        their defaults the loop is, call for call, the one without them."""
         from utils.lm_sampling import sample_next
-        from ..ops.decode import sample_tokens
+        from ..ops.decode import penalize_logits_, sample_tokens
+        penalties, min_new = _logit_processors(repetition_penalty, presence_penalty, frequency_penalty,
+                                               no_repeat_ngram, min_new_tokens, eos_id)
         philox = noise_seed is not None and temperature > 0
         B, Lp = input_ids.shape
         dev = input_ids.device
@@ -166,8 +198,18 @@ class GPT2LMModel(nn.Module):
         out = torch.full((B, max_new_tokens), fill, dtype=torch.long, device=dev)
         new_lens = torch.zeros(B, dtype=torch.long, device=dev)
         done = torch.zeros(B, dtype=torch.bool, device=dev)
+        if penalties is not None:
+            # a row's prompt and output so far: hist[b, :n[b]]; a new token lands on the padding
+            hist = torch.zeros(B, Lp + max_new_tokens, dtype=torch.int32, device=dev)
+            hist[:, :Lp] = input_ids
+            n = lens.to(device=dev, dtype=torch.int32).clone()
+            start = None if penalize_prompt else n.clone()
         logits = self.prefill(input_ids, lens, cache)
         for t in range(max_new_tokens):
+            if t < min_new:
+                logits[:, fill] = float("-inf")  # every live row has produced t tokens
+            if penalties is not None:
+                penalize_logits_(logits, hist, n, start=start, **penalties)
             if philox:
                 tok = sample_tokens(logits, temperature=temperature, top_k=top_k, top_p=top_p, seed=int(noise_seed),
                                     step=t, row_base=row_base)
@@ -175,6 +217,9 @@ class GPT2LMModel(nn.Module):
                 tok = sample_next(logits, temperature, top_k, top_p, generator)
             tok = torch.where(done, fill, tok)
             out[:, t] = tok
+            if penalties is not None:
+                hist.scatter_(1, n.long().view(B, 1), tok.to(torch.int32).view(B, 1))
+                n += 1
             new_lens += (~done).to(new_lens.dtype)
             if eos_id is not None:
                 done = done | (tok == fill)
@@ -218,7 +263,9 @@ class GPT2LMModel(nn.Module):
 
     @torch.no_grad()
     def generate_lookahead(self, input_ids, lens, max_new_tokens, *, lookahead, ngram=2, eos_id=None, cache=None,
-                           check_every=4, draft=None, return_stats=False):
+                           check_every=4, draft=None, return_stats=False, repetition_penalty=1.0,
+                           presence_penalty=0.0, frequency_penalty=0.0, no_repeat_ngram=0, min_new_tokens=0,
+                           penalize_prompt=True):
         """Greedy continuation by lookahead decoding -> (tokens [B, max_new_tokens], new_lens [B]),
         with the meanings of :meth:`generate`: its ``temperature=0`` result wherever every arg-max on
         the way is the same in both, in fewer model calls.
@@ -238,9 +285,17 @@ class GPT2LMModel(nn.Module):
         ``draft``: a callable with ``lookup_draft``'s signature ``(history [B, Lh], n [B], *, ngram,
         max_draft) -> (draft [B, max_draft], k [B])`` to use instead - ``history[b, :n[b]]`` is the
         row's prompt and output so far.  ``return_stats`` adds a dict: ``model_calls`` (iterations with
-        a live row), ``proposed`` and ``accepted`` guesses, read back once at the end."""
+        a live row), ``proposed`` and ``accepted`` guesses, read back once at the end.
+
+        The logit processors of :meth:`generate` are not available here: the guesses continue
+        repeated n-grams, which is what those penalties forbid, and the queries of a block would
+        each need a history of their own.  Any non-default value raises ``ValueError``."""
         from utils.lm_sampling import greedy
         from ..ops.decode import lookup_draft
+        if ((repetition_penalty, presence_penalty, frequency_penalty, no_repeat_ngram, min_new_tokens) != (1.0, 0.0, 0.0, 0, 0)
+                or penalize_prompt is not True):
+            raise ValueError("lookahead decoding does not take logit penalties, no_repeat_ngram, min_new_tokens or "
+                             "penalize_prompt: use generate")
         T, g, N = int(lookahead), int(ngram), int(max_new_tokens)
         if not 2 <= T <= 8:
             raise ValueError(f"lookahead must be in 2 .. 8, got {lookahead}")
@@ -316,7 +371,8 @@ class GPT2LMModel(nn.Module):
 
     @torch.no_grad()
     def beam_search(self, input_ids, lens, max_new_tokens, *, num_beams, eos_id=None, length_penalty=0.0,
-                    cache=None, check_every=16):
+                    cache=None, check_every=16, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
+                    no_repeat_ngram=0, min_new_tokens=0, penalize_prompt=True):
         """Continue right-padded prompts with beam search -> (tokens [B, W, max_new_tokens], new_lens
         [B, W], scores fp32 [B, W]), ``W = num_beams``, the beams of a prompt best first.
 
@@ -337,8 +393,17 @@ class GPT2LMModel(nn.Module):
         :meth:`generate`, a beam stops at ``eos_id`` or when the cache is full, the rest of its row
         is ``eos_id`` (0 without one), ``new_lens`` counts a closing ``eos_id``, and the host looks
         at the loop once every ``check_every`` steps (0: never).  A slot that never held a
-        hypothesis (fewer than W candidates) has score -inf, length 0 and a row of fill."""
-        from ..ops.decode import beam_step
+        hypothesis (fewer than W candidates) has score -inf, length 0 and a row of fill.
+
+        The logit processors of :meth:`generate`, with the same keywords: every beam has a history
+        row of its own, re-ordered by ``parent`` with one gather per step and extended at the group's
+        common position, and ``ops.decode.penalize_logits_`` runs on every step's logits before
+        ``beam_step`` (finished and non-existent slots are passed as parked rows).  The first step's
+        logits are one row per prompt repeated for every beam, so they are penalised once, before
+        they are expanded.  The scores are sums of the log-softmax of the processed logits."""
+        from ..ops.decode import beam_step, penalize_logits_
+        penalties, min_new = _logit_processors(repetition_penalty, presence_penalty, frequency_penalty,
+                                               no_repeat_ngram, min_new_tokens, eos_id)
         W = int(num_beams)
         if not 1 <= W <= 255:
             raise ValueError(f"num_beams must be in 1 .. 255, got {num_beams}")
@@ -356,6 +421,15 @@ class GPT2LMModel(nn.Module):
         ninf = float("-inf")
 
         logits = self.prefill(input_ids, lens, cache.slot_view(W, 0))  # the prompts, once, into slot 0
+        if min_new > 0:
+            logits[:, fill] = ninf
+        if penalties is not None:
+            Lh = Lp + T
+            plen = lens.to(device=dev, dtype=torch.int32).clone()
+            hist = torch.zeros(B, W, Lh, dtype=torch.int32, device=dev)  # a beam's prompt and output so far
+            hist[:, :, :Lp] = input_ids.unsqueeze(1)
+            start = None if penalize_prompt else plen.view(B, 1).expand(B, W).reshape(-1)
+            penalize_logits_(logits, hist[:, 0], plen, start=None if penalize_prompt else plen, **penalties)
         logits = logits.unsqueeze(1).expand(B, W, logits.shape[-1])    # beam stride 0
         glen = lens.to(device=dev, dtype=torch.int32).clone()          # the group's common length
         scores = torch.full((B, W), ninf, dtype=torch.float32, device=dev)
@@ -395,6 +469,14 @@ class GPT2LMModel(nn.Module):
             cache.lens.copy_(torch.where(active, glen.view(B, 1), -1).view(-1))
             logits = self.decode_step(token.view(-1), cache, table=(nxt.view(B * W, Lmax), W)).view(B, W, -1)
             glen = glen + (glen < Lmax).to(glen.dtype)
+            if t + 1 < min_new:
+                logits[:, :, fill] = ninf  # every live beam has produced t + 1 tokens
+            if penalties is not None:
+                # the parents' histories, then this step's tokens at the group's common position
+                hist = hist.gather(1, par.view(B, W, 1).expand(B, W, Lh))
+                hist.scatter_(2, (plen.long() + t).view(B, 1, 1).expand(B, W, 1), token.to(torch.int32).view(B, W, 1))
+                n = torch.where(active, (plen + (t + 1)).view(B, 1), -1).to(torch.int32).view(-1)
+                penalize_logits_(logits.view(B * W, -1), hist.view(B * W, Lh), n, start=start, **penalties)
         cache.lens.copy_(torch.where(active, glen.view(B, 1), -1).view(-1))
 
         # the token rows: walk the recorded parents backwards

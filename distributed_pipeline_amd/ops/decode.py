@@ -1,7 +1,8 @@
 """
 The per-token ops of GPT-2 generation: single-query attention over a K/V cache (directly, or through
 the indirection table of a beam search), the same for a block of new tokens with the guesses that
-fill it (lookahead decoding), one beam-search step, and the choice of the next token.
+fill it (lookahead decoding), one beam-search step, the choice of the next token, and the logit
+processors in front of it (repetition, presence and frequency penalty, no-repeat-n-gram ban).
 
 Attention of one decode step
 ----------------------------
@@ -143,6 +144,50 @@ fp32 or bf16 logits with last stride 1 (any row stride) and V <= 65536 on a HIP 
 per call (csrc/sample.hip), nothing read back to the host.  Anything else: the same definition in
 PyTorch with the same uniform bits, :func:`sample_tokens_ref`.  ``sample_uniforms`` returns the
 ``u_v``, so tests and tools can pin the noise bit for bit.
+
+The logit processors: ``penalize_logits_``
+------------------------------------------
+``penalize_logits_(logits [R, V], hist [R, Lh], n [R], *, start=None, repetition_penalty=1.0,
+presence_penalty=0.0, frequency_penalty=0.0, no_repeat_ngram=0) -> logits`` applies the four
+processors that read a row's token history, in place, and returns its first argument.
+
+* ``logits``: fp32 or bf16 for the kernel, last stride 1, any row stride and alignment; rows that
+  overlap in memory (a row stride below V, such as the beam-stride-0 view of a beam search's first
+  step) are refused: they would have several writers.
+* ``hist``: int32 or int64 ids, any strides; ``n`` and ``start``: any integer dtype.
+* theta = ``repetition_penalty`` > 0, a_p = ``presence_penalty``, a_f = ``frequency_penalty``, each
+  taken as fp32; g = ``no_repeat_ngram`` >= 0.
+
+The window of row r.  ``n[r] < 0`` leaves the row untouched (a parked row).  Otherwise
+``hi = min(n[r], Lh)``, ``lo = clamp(start[r], 0, Lh)`` (0 without ``start``), the window is
+``w = hist[r, lo:hi]`` and ``m = max(hi - lo, 0)``.  Nothing outside the window is read for its value;
+what lies beyond ``hi`` never influences the result.
+
+Counts and bans.  ``c(x)`` is the number of positions of w that hold x.  With g >= 1 the banned set
+is ``Bn = { w[i] : g - 1 <= i < m and w[i-g+1 .. i-1] == w[m-g+1 .. m-1] }``: every id that would
+complete a g-gram the window already holds.  g = 1 bans every id of the window; ``m < g`` or g = 0
+bans nothing.
+
+The update, for every x in ``[0, V)`` with ``c(x) >= 1``, exactly once per distinct x, each step one
+fp32 rounding:
+
+1. ``s = fp32(logits[r, x])``;
+2. ``s = s * theta if s < 0 else s / theta`` (correctly rounded division);
+3. ``s = s - (a_p + a_f * fp32(c(x)))``: the multiply and the add are separate roundings (no FMA);
+4. ``s = -inf`` if x is in Bn;
+5. ``logits[r, x] = s`` rounded to the dtype of ``logits`` (round to nearest even).
+
+So the order is repetition penalty, then presence / frequency penalty, then the ban.  Ids of the
+window outside ``[0, V)`` take part in the n-gram comparison and write nothing.  Every other element
+keeps its bits; a NaN stays a NaN unless its id is banned.  The window is whatever the caller puts
+into ``hist`` - prompt and output alike, or with ``start`` the output alone - where conventions that
+penalise "output only" or "prompt and output" differ in nothing else.
+
+fp32 or bf16 logits on a HIP device with ``Lh <= 2048``: one launch of csrc/logit_penalty.hip, one
+workgroup per row, no sweep over V, no workspace, no atomics, nothing read back.  Anything else (CPU,
+other dtypes, a longer history): :func:`penalize_logits_ref`, the same definition with the same fp32
+operations in PyTorch over chunks of rows; it gives the kernel's bits.  With every scalar at its
+default nothing is done at all.
 """
 import math
 import struct
@@ -501,3 +546,113 @@ def beam_step(logits, scores, finished, *, eos_id=-1, fill=0, return_logp=False)
             if out is not None:
                 return tuple(out) if return_logp else tuple(out[:4])
     return beam_step_ref(logits, scores, finished, eos_id=eos_id, fill=fill, return_logp=return_logp)
+
+
+# ---- penalize_logits_ ---------------------------------------------------------------------------
+
+PENALTY_MAX_HIST = 2048  # LP_MAX_L of csrc/logit_penalty.hip
+
+
+def _check_penalty(logits, hist, n, start, theta, g):
+    if logits.dim() != 2 or hist.dim() != 2 or n.dim() != 1:
+        raise ValueError(f"logits must be [R, V], hist [R, Lh] and n [R], got {tuple(logits.shape)}, "
+                         f"{tuple(hist.shape)}, {tuple(n.shape)}")
+    R, V = logits.shape
+    if hist.shape[0] != R or n.shape[0] != R or (start is not None and tuple(start.shape) != (R,)):
+        raise ValueError(f"hist, n and start must have the {R} rows of logits, got {tuple(hist.shape)}, "
+                         f"{tuple(n.shape)}" + ("" if start is None else f", {tuple(start.shape)}"))
+    for name, t in (("hist", hist), ("n", n), ("start", start)):
+        if t is not None and (t.is_floating_point() or t.is_complex() or t.dtype == torch.bool):
+            raise ValueError(f"{name} must hold integers, got {t.dtype}")
+    if not logits.is_floating_point():
+        raise ValueError(f"logits must be floating point, got {logits.dtype}")
+    if not theta > 0:
+        raise ValueError(f"repetition_penalty must be > 0, got {theta}")
+    if g < 0:
+        raise ValueError(f"no_repeat_ngram must be >= 0, got {g}")
+    if V > 1 and logits.stride(1) != 1:
+        raise ValueError("logits must have last stride 1 (the op works in place)")
+    if R > 1 and logits.stride(0) < V:
+        raise ValueError(f"the rows of logits overlap in memory (row stride {logits.stride(0)} < V = {V}): "
+                         "an in-place update would have several writers")
+
+
+@torch.no_grad()
+def penalize_logits_ref(logits, hist, n, *, start=None, repetition_penalty=1.0, presence_penalty=0.0,
+                        frequency_penalty=0.0, no_repeat_ngram=0, chunk_elems=1 << 24):
+    """The definition in PyTorch (any device, any float dtype), in place, over chunks of rows whose
+    ``[rows, Lh, Lh]`` comparison holds at most ``chunk_elems`` elements.  The same fp32 operations as
+    the kernel, one rounding each."""
+    g = int(no_repeat_ngram)
+    _check_penalty(logits, hist, n, start, float(repetition_penalty), g)
+    R, V = logits.shape
+    Lh = hist.shape[1]
+    if R == 0 or V == 0 or Lh == 0:
+        return logits
+    dev = logits.device
+    # one-element device tensors: a division by one is a true division, not a multiply by the reciprocal
+    theta, a_p, a_f = (torch.full((1,), float(x), dtype=torch.float32, device=dev)
+                       for x in (repetition_penalty, presence_penalty, frequency_penalty))
+    n = n.to(dev).long()
+    hi = n.clamp(0, Lh).view(R, 1)
+    lo = torch.zeros_like(hi) if start is None else start.to(dev).long().clamp(0, Lh).view(R, 1)
+    pos = torch.arange(Lh, device=dev).view(1, Lh)
+    inside = (pos >= lo) & (pos < hi) & (n >= 0).view(R, 1)
+    below = torch.ones(Lh, Lh, dtype=torch.bool, device=dev).tril(-1)  # [i, j]: j < i
+    step = max(1, int(chunk_elems) // (Lh * Lh))
+    for r0 in range(0, R, step):
+        h = hist[r0:r0 + step].to(dev).long()
+        rows = h.shape[0]
+        inw = inside[r0:r0 + step]
+        eq = (h.unsqueeze(2) == h.unsqueeze(1)) & inw.unsqueeze(2) & inw.unsqueeze(1)  # [r, i, j]
+        count = eq.sum(-1)
+        valid = inw & ~(eq & below).any(-1) & (h >= 0) & (h < V)  # the first occurrence of an id of [0, V)
+        banned = torch.zeros_like(inw)
+        if g >= 1:
+            src = inw & (pos - lo[r0:r0 + step] >= g - 1)  # none when the window is shorter than g
+            for t in range(g - 1 if g <= Lh else 0):
+                mine = h.gather(1, (pos - (g - 1) + t).clamp(0, Lh - 1).expand(rows, Lh))
+                last = h.gather(1, (hi[r0:r0 + step] - (g - 1) + t).clamp(0, Lh - 1))
+                src = src & (mine == last)
+            banned = (eq & src.unsqueeze(1)).any(-1)
+        rr, ii = valid.nonzero(as_tuple=True)
+        if rr.numel() == 0:
+            continue
+        x = h[rr, ii]
+        view = logits[r0:r0 + step]
+        s = view[rr, x].float()
+        s = torch.where(s < 0, s * theta, s / theta)
+        s = s - (a_p + a_f * count[rr, ii].float())
+        s = torch.where(banned[rr, ii], float("-inf"), s)
+        view[rr, x] = s.to(logits.dtype)
+    return logits
+
+
+def _as_i32(t, lowest, highest, dev):
+    """``t`` as the contiguous int32 device tensor the kernel reads; values are clamped first, which
+    the definition does anyway, so a wide dtype cannot wrap."""
+    if t.dtype == torch.int32 and t.is_contiguous() and t.device == dev:
+        return t
+    return t.to(dev).clamp(lowest, highest).to(torch.int32).contiguous()
+
+
+@torch.no_grad()
+def penalize_logits_(logits, hist, n, *, start=None, repetition_penalty=1.0, presence_penalty=0.0,
+                     frequency_penalty=0.0, no_repeat_ngram=0):
+    """Repetition, presence and frequency penalty and the no-repeat-n-gram ban on ``logits`` [R, V],
+    in place -> ``logits``: the module docstring has the definition."""
+    theta, a_p, a_f, g = float(repetition_penalty), float(presence_penalty), float(frequency_penalty), int(no_repeat_ngram)
+    _check_penalty(logits, hist, n, start, theta, g)
+    if theta == 1.0 and a_p == 0.0 and a_f == 0.0 and g == 0:
+        return logits
+    Lh = hist.shape[1]
+    if logits.is_cuda:
+        ext = get_ext()  # raises on a GPU without the built extension: no quiet fall-back
+        if (ext is not None and logits.dtype in (torch.float32, torch.bfloat16) and Lh <= PENALTY_MAX_HIST
+                and hist.dtype in (torch.int32, torch.int64) and hist.device == logits.device):
+            dev = logits.device
+            if ext.penalize_logits(logits, hist, _as_i32(n, -1, Lh, dev),
+                                   None if start is None else _as_i32(start, 0, Lh, dev), theta, a_p, a_f, g):
+                return logits
+    return penalize_logits_ref(logits, hist, n, start=start, repetition_penalty=theta, presence_penalty=a_p,
+                               frequency_penalty=a_f, no_repeat_ngram=g)

@@ -23,6 +23,13 @@ it ignores ``--temperature`` and ``--seed`` and excludes ``--top_k``, ``--top_p`
 decoding's own output, T tokens per model call - the last one and T - 1 guesses copied from behind the
 latest earlier occurrence of the row's last ``--lookup_ngram`` tokens - of which the verified prefix is
 kept.  The run prints the model calls it made and how many guesses were accepted.
+
+``--repetition_penalty``, ``--presence_penalty``, ``--frequency_penalty`` and ``--no_repeat_ngram`` keep a
+continuation from repeating itself: every step's logits go through ``ops.decode.penalize_logits_`` (one
+kernel on a GPU) before the token is chosen, over the prompt and the tokens generated so far, or with
+``--penalize_prompt false`` over the generated tokens alone.  ``--min_new_tokens M`` holds ``--eos_id`` off
+for the first M tokens.  They combine with sampling, ``--noise philox`` and ``--num_beams`` and exclude
+``--lookahead``.
 """
 import json
 import os
@@ -84,7 +91,7 @@ def main(namespace):
             if args.num_beams > 1:
                 beams, beam_lens, beam_scores = model.beam_search(
                     ids[:, :Lp].contiguous(), lens, Ln, num_beams=args.num_beams, eos_id=eos,
-                    length_penalty=args.length_penalty)
+                    length_penalty=args.length_penalty, **args.logit_processors())
                 beams, beam_lens, beam_scores = beams.cpu(), beam_lens.cpu(), beam_scores.cpu()
                 toks, new_lens = beams[:, 0], beam_lens[:, 0]
             elif args.lookahead:
@@ -97,7 +104,8 @@ def main(namespace):
             else:
                 toks, new_lens = model.generate(ids[:, :Lp].contiguous(), lens, Ln, temperature=args.temperature,
                                                 top_k=args.top_k, top_p=args.top_p, eos_id=eos, generator=gen,
-                                                noise_seed=args.seed if args.noise == "philox" else None, row_base=n)
+                                                noise_seed=args.seed if args.noise == "philox" else None, row_base=n,
+                                                **args.logit_processors())
             ids, toks, new_lens = ids.cpu(), toks.cpu(), new_lens.cpu()
 
             def cut(row, length):
