@@ -73,6 +73,10 @@ class ContinueSettings(S):
     penalize_prompt: bool \
         = _(True, "The penalties and the n-gram ban see the prompt as well as the tokens generated so far; "
                   "false: the generated tokens alone.")
+    logprobs: bool \
+        = _(False, "Also write 'logprobs': each continuation token's log-probability under the step's logits "
+                   "(after the penalties, before temperature, top_k and top_p). Excludes --num_beams > 1 and "
+                   "--lookahead.")
     out_path: str \
         = _("", "Output .jsonl file (default: generated_<checkpoint>_seed<seed>.jsonl next to the checkpoint).")
     precision: Choice("bf16", "fp32") \
@@ -159,6 +163,9 @@ class GenerateSettings(
             raise ValueError("--lookahead excludes --repetition_penalty, --presence_penalty, --frequency_penalty, "
                              "--no_repeat_ngram, --min_new_tokens and --penalize_prompt: its guesses continue "
                              "repeated n-grams")
+        if self.logprobs and (self.num_beams > 1 or self.lookahead):
+            raise ValueError("--logprobs comes from generate's own loop: it excludes --num_beams > 1 (see "
+                             "--keep_beams for beam scores) and --lookahead")
         if self.prompt_len < 1 or self.max_new_tokens < 1:
             raise ValueError("--prompt_len and --max_new_tokens must be >= 1")
         if self.prompt_len + self.max_new_tokens > self.seq_len:

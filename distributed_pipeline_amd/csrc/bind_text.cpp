@@ -1,6 +1,6 @@
 // Bindings of the generation and text-metric kernels: token sampling (sample.hip), the beam-search
-// step (beam_step.hip), the logit processors (logit_penalty.hip) and the
-// per-group n-gram / LCS counts (ngram_match.hip, ngram_distinct.hip, lcs.hip).
+// step (beam_step.hip), the logit processors (logit_penalty.hip), teacher-forced scoring
+// (token_stats.hip) and the per-group n-gram / LCS counts (ngram_match.hip, ngram_distinct.hip, lcs.hip).
 #include <limits.h>
 
 #include "bind_util.h"
@@ -117,6 +117,32 @@ static bool penalize_logits(at::Tensor& logits, const at::Tensor& hist, const at
                                    (float)alpha_f, (int)std::min<int64_t>(ngram, INT_MAX), cur_stream());
 }
 
+// Teacher-forced statistics of logits [R, V] against targets [R] (csrc/token_stats.hip; the definition is in
+// ops/decode.py): logits fp32 or bf16 (last stride 1, any row stride >= 0), targets int32 or int64 (any
+// stride) -> [logp fp32, rank int32, entropy fp32, top1 int32], all [R]; None for a case the kernel does
+// not cover (CPU tensor, dtype, V > 65536, V < 1, a last stride other than 1, R == 0).
+static c10::optional<std::vector<at::Tensor>> token_stats(const at::Tensor& logits, const at::Tensor& targets) {
+  TORCH_CHECK(logits.dim() == 2 && targets.dim() == 1 && targets.size(0) == logits.size(0),
+              "token_stats: logits [R, V], targets [R]");
+  const int64_t R = logits.size(0), V = logits.size(1);
+  if (!logits.is_cuda() || (logits.scalar_type() != at::kFloat && logits.scalar_type() != at::kBFloat16))
+    return c10::nullopt;
+  if (targets.device() != logits.device() || (targets.scalar_type() != at::kInt && targets.scalar_type() != at::kLong))
+    return c10::nullopt;
+  if (R < 1 || R > 0x7fffffffLL || V < 1 || V > 65536 || (V > 1 && logits.stride(1) != 1) || logits.stride(0) < 0)
+    return c10::nullopt;
+  const c10::DeviceGuard guard(logits.device());
+  auto opt = at::TensorOptions().device(logits.device());
+  std::vector<at::Tensor> out{at::empty({R}, opt.dtype(at::kFloat)), at::empty({R}, opt.dtype(at::kInt)),
+                              at::empty({R}, opt.dtype(at::kFloat)), at::empty({R}, opt.dtype(at::kInt))};
+  const bool ok = dpa::launch_token_stats(
+      logits.data_ptr(), logits.scalar_type() == at::kBFloat16, logits.stride(0), R, (int)V, targets.data_ptr(),
+      targets.scalar_type() == at::kLong, targets.stride(0), out[0].data_ptr<float>(), out[1].data_ptr<int>(),
+      out[2].data_ptr<float>(), out[3].data_ptr<int>(), cur_stream());
+  if (!ok) return c10::nullopt;
+  return out;
+}
+
 // ---- per-group token ops: tokens [G, K, L] int32 / int64, lens [G, K] int32 -> int32 counts ----
 static void check_token_group(const at::Tensor& tokens, const at::Tensor& lens, const char* op) {
   CHECK_DEV(tokens); CHECK_CONTIG(tokens); CHECK_DEV(lens); CHECK_CONTIG(lens);
@@ -182,6 +208,9 @@ void dpa::register_text(pybind11::module& m) {
         "repetition / presence / frequency penalty and no-repeat-n-gram ban on logits, in place -> True | False (case not covered)",
         py::arg("logits"), py::arg("hist"), py::arg("n"), py::arg("start"), py::arg("theta"), py::arg("alpha_p"),
         py::arg("alpha_f"), py::arg("ngram"));
+  m.def("token_stats", &token_stats,
+        "log-probability and rank of a target id, entropy and arg-max of every logits row -> [logp, rank, entropy, top1] | None (case not covered)",
+        py::arg("logits"), py::arg("targets"));
   m.def("ngram_matches", &ngram_matches,
         "clipped 1..4-gram match counts of every sequence pair of a group -> int32 [G, K, K, 4] | None (shape not covered)",
         py::arg("tokens"), py::arg("lens"));

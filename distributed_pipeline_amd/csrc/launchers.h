@@ -264,6 +264,18 @@ bool launch_beam_step(const void* logits, bool bf16, int64_t stride_b, int64_t s
                       float* new_scores, int* parent, int64_t* token, uint8_t* new_finished, float* logp,
                       hipStream_t st);
 
+// ---- token_stats.hip: teacher-forced statistics of logits rows against target ids (scoring) ----
+// For every row r of logits ([R][V] fp32 or bf16, rows row_stride >= 0 elements apart, any alignment) and
+// its target t = targets[r * t_stride] (int32, or int64 with t64): with s = fp32(logit), NaN -> -inf and
+// -0 -> +0, m = max s, Z = sum exp(s - m): logp[r] = (s_t - m) - log Z, rank[r] = #{s_v > s_t} +
+// #{v < t : s_v == s_t}, entropy[r] = log Z - (sum exp(s_v - m) (s_v - m)) / Z (an id at -inf adds 0),
+// top1[r] = the lowest id holding m.  m not finite: logp and entropy NaN.  t outside [0, V): logp 0 and
+// rank -1.  One launch, one workgroup per row, no workspace, no atomics.  false, with no launch: V outside
+// 1 .. 65536, R outside 1 .. 2^31 - 1, a negative row stride or a null pointer.
+bool launch_token_stats(const void* logits, bool bf16, int64_t row_stride, int64_t R, int V, const void* targets,
+                        bool t64, int64_t t_stride, float* logp, int* rank, float* entropy, int* top1,
+                        hipStream_t st);
+
 // ---- sample.hip: temperature / top-k / top-p next-token draw (GPT-2 generation) ---------
 // tokens[b] = the id drawn for row b of logits ([B][V] fp32 or bf16, rows row_stride elements apart, any
 // alignment): s = logit / temperature, top_k (0 < top_k < V, ties with the k-th kept), top_p (0 < top_p <

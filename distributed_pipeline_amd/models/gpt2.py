@@ -163,7 +163,7 @@ class GPT2LMModel(nn.Module):
     def generate(self, input_ids, lens, max_new_tokens, *, temperature=1.0, top_k=0, top_p=0.0, eos_id=None,
                  generator=None, cache=None, check_every=16, noise_seed=None, row_base=0, repetition_penalty=1.0,
                  presence_penalty=0.0, frequency_penalty=0.0, no_repeat_ngram=0, min_new_tokens=0,
-                 penalize_prompt=True):
+                 penalize_prompt=True, return_logprobs=False):
         """Continue right-padded prompts -> (tokens [B, max_new_tokens], new_lens [B]).
 
         ``temperature == 0`` is greedy (ties to the lowest id); otherwise ``logits / temperature``,
@@ -184,9 +184,15 @@ class GPT2LMModel(nn.Module):
         through ``ops.decode.penalize_logits_`` before the token is chosen; ``penalize_prompt=False``
         leaves the prompt out of the window (``start = lens``).  ``min_new_tokens = M`` sets the
         ``eos_id`` logit of a row that has produced fewer than M tokens to -inf first.  With all at
-        their defaults the loop is, call for call, the one without them."""
+        their defaults the loop is, call for call, the one without them.
+
+        ``return_logprobs=True`` adds a third result, ``logprobs`` fp32 [B, max_new_tokens]: entry t is
+        the log-probability of the token chosen at step t under the step's processed logits - after
+        ``min_new_tokens`` and the penalties, before temperature, ``top_k`` and ``top_p`` - as
+        ``ops.decode.token_stats`` gives it, and 0 from the step a row is done.  Tokens and lengths are
+        those of the call without it."""
         from utils.lm_sampling import sample_next
-        from ..ops.decode import penalize_logits_, sample_tokens
+        from ..ops.decode import penalize_logits_, sample_tokens, token_stats
         penalties, min_new = _logit_processors(repetition_penalty, presence_penalty, frequency_penalty,
                                                no_repeat_ngram, min_new_tokens, eos_id)
         philox = noise_seed is not None and temperature > 0
@@ -198,6 +204,7 @@ class GPT2LMModel(nn.Module):
         out = torch.full((B, max_new_tokens), fill, dtype=torch.long, device=dev)
         new_lens = torch.zeros(B, dtype=torch.long, device=dev)
         done = torch.zeros(B, dtype=torch.bool, device=dev)
+        logprobs = torch.zeros(B, max_new_tokens, dtype=torch.float32, device=dev) if return_logprobs else None
         if penalties is not None:
             # a row's prompt and output so far: hist[b, :n[b]]; a new token lands on the padding
             hist = torch.zeros(B, Lp + max_new_tokens, dtype=torch.int32, device=dev)
@@ -215,6 +222,8 @@ class GPT2LMModel(nn.Module):
                                     step=t, row_base=row_base)
             else:
                 tok = sample_next(logits, temperature, top_k, top_p, generator)
+            if return_logprobs:
+                logprobs[:, t] = token_stats(logits, torch.where(done, -1, tok))[0]  # a done row: "ignore", 0
             tok = torch.where(done, fill, tok)
             out[:, t] = tok
             if penalties is not None:
@@ -231,7 +240,87 @@ class GPT2LMModel(nn.Module):
                 break
             logits = self.decode_step(tok, cache)
         cache.lens.masked_fill_(done, -1)
-        return out, new_lens
+        return (out, new_lens, logprobs) if return_logprobs else (out, new_lens)
+
+    # ---- teacher-forced scoring (inference only) -----------------------------------------
+
+    @torch.no_grad()
+    def score(self, input_ids, lens=None, *, start=None):
+        """Teacher-forced statistics of every scored token of right-padded ``input_ids`` [B, L] -> a
+        dict of [B, L - 1] tensors whose column j speaks of token ``input_ids[b, j + 1]`` given the
+        tokens in front of it: ``logp`` fp32 (its log-probability, nats), ``rank`` int32 (its 0-based
+        place among the V ids, ties by id), ``entropy`` fp32 (of the model's distribution there),
+        ``top1`` int64 (the model's arg-max) and ``mask`` bool.
+
+        Position ``p = j + 1`` is scored iff ``max(start[b], 1) <= p < lens[b]``; ``start`` defaults to
+        1 (everything but the first token) and ``lens`` to L, and a value outside ``[0, L]`` raises.
+        Outside the mask ``logp = 0``, ``rank = -1``, ``entropy = 0`` and ``top1 = -1``, and ids at or
+        behind ``lens[b]`` are never looked at.
+
+        One causal forward in eval behaviour whatever ``self.training`` is (the stack of
+        :meth:`prefill`; on the native bf16 path L is padded to a multiple of 64, which causality
+        hides), then only the hidden rows inside the mask go through the head: chunks of at most
+        256 MiB of logits, ``ops.linear`` and ``ops.decode.token_stats`` each.  The positions are
+        gathered with one ``nonzero`` (a host synchronisation)."""
+        from ..ops.decode import token_stats
+        if input_ids.dim() != 2:
+            raise ValueError(f"input_ids must be [B, L], got {tuple(input_ids.shape)}")
+        B, L = input_ids.shape
+        dev = input_ids.device
+        if L > self.cfg["max_position_embeddings"]:
+            raise ValueError(f"L = {L} exceeds max_position_embeddings {self.cfg['max_position_embeddings']}")
+
+        def bound(x, default, name):
+            if x is None:
+                return torch.full((B,), default, dtype=torch.long, device=dev)
+            x = torch.as_tensor(x, device=dev)
+            if x.is_floating_point() or x.dtype == torch.bool or tuple(x.shape) != (B,):
+                raise ValueError(f"{name} must hold {B} integers, got {x.dtype} {tuple(x.shape)}")
+            x = x.long()
+            if B and bool(((x < 0) | (x > L)).any()):
+                raise ValueError(f"{name} must lie in 0 .. L = {L}")
+            return x
+
+        lens, start = bound(lens, L, "lens"), bound(start, 1, "start")
+        n = max(L - 1, 0)
+        res = {"logp": torch.zeros(B, n, dtype=torch.float32, device=dev),
+               "rank": torch.full((B, n), -1, dtype=torch.int32, device=dev),
+               "entropy": torch.zeros(B, n, dtype=torch.float32, device=dev),
+               "top1": torch.full((B, n), -1, dtype=torch.long, device=dev),
+               "mask": torch.zeros(B, n, dtype=torch.bool, device=dev)}
+        if B == 0 or n == 0:
+            return res
+        p = torch.arange(1, L, device=dev).view(1, n)
+        mask = (p >= start.clamp(min=1).view(B, 1)) & (p < lens.view(B, 1))
+        res["mask"] = mask
+        bi, ji = mask.nonzero(as_tuple=True)
+        if bi.numel() == 0:
+            return res
+
+        dt = self.compute_dtype
+        # what stands at or behind lens[b] is padding of any content: it never reaches the embedding
+        ids = torch.where(torch.arange(L, device=dev).view(1, L) < lens.view(B, 1), input_ids, 0)
+        Lr = L
+        if ids.is_cuda and dt == torch.bfloat16 and L % 64:
+            # ops.attention's kernels take L % 64 == 0: pad on the right, which causality hides
+            Lr = min(-(-L // 64) * 64, self.cfg["max_position_embeddings"])
+            ids = torch.nn.functional.pad(ids, (0, Lr - L))
+        heads = self.cfg["num_heads"]
+        ln0 = self.h[0].ln_1
+        x, a = ops.residual_layernorm(self.wte(ids, dt), None, ln0.weight, ln0.bias, 0.0, ln0.eps, False,
+                                      pos=self.wpe(self.position_ids[:, :Lr], dt))
+        a = self._blocks(x, a, lambda i, qkv: ops.attention(qkv, heads, 0.0, True, False))
+
+        rows = a[bi, ji]                 # [N, H]: the hidden state in front of each scored token
+        tgt = input_ids[bi, ji + 1]
+        V = self.wte.weight.shape[0]
+        step = max(1, (256 << 20) // (V * rows.element_size()))
+        for r0 in range(0, rows.shape[0], step):
+            logits = ops.linear(rows[r0:r0 + step], self.wte.weight)
+            lp, rk, en, t1 = token_stats(logits, tgt[r0:r0 + step])
+            at = (bi[r0:r0 + step], ji[r0:r0 + step])
+            res["logp"][at], res["rank"][at], res["entropy"][at], res["top1"][at] = lp, rk, en, t1.long()
+        return res
 
     @torch.no_grad()
     def decode_block(self, tokens, cache, counts=None):

@@ -1,8 +1,9 @@
 """
 The per-token ops of GPT-2 generation: single-query attention over a K/V cache (directly, or through
 the indirection table of a beam search), the same for a block of new tokens with the guesses that
-fill it (lookahead decoding), one beam-search step, the choice of the next token, and the logit
-processors in front of it (repetition, presence and frequency penalty, no-repeat-n-gram ban).
+fill it (lookahead decoding), one beam-search step, the choice of the next token, the logit
+processors in front of it (repetition, presence and frequency penalty, no-repeat-n-gram ban), and
+the statistics of a logits row against a given token (teacher-forced scoring).
 
 Attention of one decode step
 ----------------------------
@@ -188,6 +189,34 @@ workgroup per row, no sweep over V, no workspace, no atomics, nothing read back.
 other dtypes, a longer history): :func:`penalize_logits_ref`, the same definition with the same fp32
 operations in PyTorch over chunks of rows; it gives the kernel's bits.  With every scalar at its
 default nothing is done at all.
+
+Teacher-forced scoring: ``token_stats``
+---------------------------------------
+``token_stats(logits [R, V], targets [R]) -> (logp fp32 [R], rank int32 [R], entropy fp32 [R], top1
+int32 [R])``: how the row's distribution stands to one given id.  Per row, with target t:
+
+1. ``s_v = fp32(logit_v)``.  A NaN becomes -inf and -0 becomes +0 (``beam_step``'s conditioning).
+2. ``m = max_v s_v``; ``top1`` is the lowest id holding m.  If m is not finite (all -inf, or any +inf),
+   ``logp`` and ``entropy`` are NaN; ``rank`` and ``top1`` are comparisons only and stay defined.
+3. ``Z = sum_v exp(s_v - m)`` with the accurate ``expf``, ``lz = logf(Z)`` and ``logp = (s_t - m) - lz``,
+   the expression ``beam_step`` uses for a pick's term.  A target logit of -inf gives -inf.
+4. ``entropy = lz - (sum_v exp(s_v - m) (s_v - m)) / Z``, in nats; an id with ``s_v = -inf``
+   contributes exactly 0 (no ``0 * -inf``).
+5. ``rank = #{v : s_v > s_t} + #{v < t : s_v == s_t}``: 0-based, the target's place in the order (value
+   descending, id ascending) - the repository's tie rule - so ``rank == 0`` iff ``top1 == t``.
+6. t outside ``[0, V)`` is how a caller says "ignore": ``logp = 0`` and ``rank = -1``; ``entropy`` and
+   ``top1`` are still the row's.
+
+Both sums are fp32 in an order that is fixed per path (the kernel: per thread in register order, then
+lanes, then waves; PyTorch: ``sum``).  ``targets`` holds integers of any dtype and stride; an int64
+value beyond 32 bits is outside.
+
+fp32 or bf16 logits with last stride 1 (any row stride and alignment) and ``1 <= V <= 65536`` on a HIP
+device: one launch of csrc/token_stats.hip, one workgroup per row, the row read once into registers,
+one 4-byte store per output and row, no workspace, no atomics, nothing read back: two calls agree bit
+for bit.  Anything else (CPU, other dtypes, a larger V): :func:`token_stats_ref`, the same definition
+in fp32 PyTorch over chunks of rows.  The two paths may differ by fp32 rounding in the two floats;
+the two integers are exact on both.
 """
 import math
 import struct
@@ -656,3 +685,73 @@ def penalize_logits_(logits, hist, n, *, start=None, repetition_penalty=1.0, pre
                 return logits
     return penalize_logits_ref(logits, hist, n, start=start, repetition_penalty=theta, presence_penalty=a_p,
                                frequency_penalty=a_f, no_repeat_ngram=g)
+
+
+# ---- token_stats --------------------------------------------------------------------------------
+
+STATS_REF_ELEMS = 1 << 22  # fp32 scores one chunk of rows of token_stats_ref may hold (16 MiB per temporary)
+
+
+def _check_token_stats(logits, targets):
+    if logits.dim() != 2 or targets.dim() != 1 or targets.shape[0] != logits.shape[0]:
+        raise ValueError(f"logits must be [R, V] and targets [R], got {tuple(logits.shape)}, {tuple(targets.shape)}")
+    if not logits.is_floating_point():
+        raise ValueError(f"logits must be floating point, got {logits.dtype}")
+    if targets.is_floating_point() or targets.is_complex() or targets.dtype == torch.bool:
+        raise ValueError(f"targets must hold integers, got {targets.dtype}")
+    if logits.shape[1] < 1:
+        raise ValueError("logits must have V >= 1")
+
+
+@torch.no_grad()
+def token_stats_ref(logits, targets, *, chunk_elems=STATS_REF_ELEMS):
+    """The definition in fp32 PyTorch (any device, any float dtype) -> (logp fp32, rank int32, entropy
+    fp32, top1 int32), all [R], over chunks of rows that hold at most ``chunk_elems`` scores."""
+    _check_token_stats(logits, targets)
+    R, V = logits.shape
+    dev = logits.device
+    ninf, nan = float("-inf"), float("nan")
+    logp = torch.empty(R, dtype=torch.float32, device=dev)
+    ent = torch.empty(R, dtype=torch.float32, device=dev)
+    rank = torch.empty(R, dtype=torch.int32, device=dev)
+    top1 = torch.empty(R, dtype=torch.int32, device=dev)
+    ids = torch.arange(V, device=dev).view(1, V)
+    step = max(1, int(chunk_elems) // V)
+    for r0 in range(0, R, step):
+        s = logits[r0:r0 + step].float()
+        s = torch.where(torch.isnan(s), ninf, s) + 0.0  # -0 -> +0
+        t = targets[r0:r0 + step].to(dev).long().view(-1, 1)
+        scored = ((t >= 0) & (t < V)).view(-1)
+        tc = t.clamp(0, V - 1)
+        m = s.amax(-1, keepdim=True)
+        fin = torch.isfinite(m).view(-1)
+        st = s.gather(1, tc)
+        d = s - m
+        p = torch.exp(d)
+        Z = p.sum(-1)
+        lz = torch.log(Z)
+        S = torch.where(d > ninf, p * d, 0.0).sum(-1)
+        lp = (st - m).view(-1) - lz
+        logp[r0:r0 + step] = torch.where(scored, torch.where(fin, lp, nan), 0.0)
+        ent[r0:r0 + step] = torch.where(fin, lz - S / Z, nan)
+        ahead = (s > st).sum(-1) + ((s == st) & (ids < tc)).sum(-1)
+        rank[r0:r0 + step] = torch.where(scored, ahead, -1).to(torch.int32)
+        top1[r0:r0 + step] = torch.where(s == m, ids, V).amin(-1).to(torch.int32)
+    return logp, rank, ent, top1
+
+
+@torch.no_grad()
+def token_stats(logits, targets):
+    """-> (logp fp32 [R], rank int32 [R], entropy fp32 [R], top1 int32 [R]): the module docstring has
+    the definition."""
+    _check_token_stats(logits, targets)
+    if logits.is_cuda:
+        ext = get_ext()  # raises on a GPU without the built extension: no quiet fall-back
+        if ext is not None and logits.dtype in (torch.float32, torch.bfloat16) and logits.shape[0] > 0:
+            t = targets.to(logits.device)
+            if t.dtype not in (torch.int32, torch.int64):
+                t = t.long()
+            out = ext.token_stats(logits, t)
+            if out is not None:
+                return tuple(out)
+    return token_stats_ref(logits, targets)

@@ -30,6 +30,11 @@ kernel on a GPU) before the token is chosen, over the prompt and the tokens gene
 ``--penalize_prompt false`` over the generated tokens alone.  ``--min_new_tokens M`` holds ``--eos_id`` off
 for the first M tokens.  They combine with sampling, ``--noise philox`` and ``--num_beams`` and exclude
 ``--lookahead``.
+
+``--logprobs true`` adds ``logprobs`` to each line, cut like ``continuation``: every token's log-probability
+under its step's logits after the penalties and before temperature, ``--top_k`` and ``--top_p``
+(``GPT2LMModel.generate(return_logprobs=True)``; ``python -m run.score --path`` gives the same numbers from a
+teacher-forced forward when no penalty is set).  It excludes ``--num_beams > 1`` and ``--lookahead``.
 """
 import json
 import os
@@ -102,10 +107,13 @@ def main(namespace):
                     look[key] += val
                 look["tokens"] += int(new_lens.sum())
             else:
-                toks, new_lens = model.generate(ids[:, :Lp].contiguous(), lens, Ln, temperature=args.temperature,
-                                                top_k=args.top_k, top_p=args.top_p, eos_id=eos, generator=gen,
-                                                noise_seed=args.seed if args.noise == "philox" else None, row_base=n,
-                                                **args.logit_processors())
+                res = model.generate(ids[:, :Lp].contiguous(), lens, Ln, temperature=args.temperature,
+                                     top_k=args.top_k, top_p=args.top_p, eos_id=eos, generator=gen,
+                                     noise_seed=args.seed if args.noise == "philox" else None, row_base=n,
+                                     **args.logit_processors(), **({"return_logprobs": True} if args.logprobs else {}))
+                toks, new_lens = res[:2]
+                if args.logprobs:
+                    logprobs = res[2].cpu()
             ids, toks, new_lens = ids.cpu(), toks.cpu(), new_lens.cpu()
 
             def cut(row, length):
@@ -120,6 +128,8 @@ def main(namespace):
                     live = [w for w in range(args.num_beams) if beam_scores[i, w] > float("-inf")]
                     line["beams"] = [cut(beams[i, w], beam_lens[i, w]) for w in live]
                     line["beam_scores"] = [float(beam_scores[i, w]) for w in live]
+                if args.logprobs:
+                    line["logprobs"] = [float(x) for x in logprobs[i, :len(line["continuation"])]]
                 fout.write(json.dumps(line) + "\n")
             n += ids.shape[0]
     if args.lookahead:
