@@ -77,6 +77,10 @@ class ContinueSettings(S):
         = _(False, "Also write 'logprobs': each continuation token's log-probability under the step's logits "
                    "(after the penalties, before temperature, top_k and top_p). Excludes --num_beams > 1 and "
                    "--lookahead.")
+    kv_dtype: Choice("bf16", "fp8") \
+        = _("bf16", "Storage of the K/V cache. fp8: one byte per element (OCP e4m3fn codes and one power-of-two "
+                    "exponent per cached row), half the memory and half the bytes a decode step reads; the "
+                    "continuations can differ from bf16's. Excludes --num_beams > 1 and --lookahead.")
     out_path: str \
         = _("", "Output .jsonl file (default: generated_<checkpoint>_seed<seed>.jsonl next to the checkpoint).")
     precision: Choice("bf16", "fp32") \
@@ -121,6 +125,11 @@ class GenerateSettings(
             raise ValueError(f"run.generate continues prompts with the gpt2 model, not {self.model!r}")
         if self.noise not in ("torch", "philox"):
             raise ValueError(f"--noise must be torch or philox, got {self.noise!r}")
+        if self.kv_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"--kv_dtype must be bf16 or fp8, got {self.kv_dtype!r}")
+        if self.kv_dtype == "fp8" and (self.num_beams > 1 or self.lookahead > 0):
+            raise ValueError("--kv_dtype fp8 is served by generate's own loop: the table (--num_beams > 1) and "
+                             "block (--lookahead) decode kernels have no fp8 variant")
         if not 0.0 <= self.top_p <= 1.0:
             raise ValueError(f"--top_p must be in [0, 1], got {self.top_p}")
         if self.temperature < 0:

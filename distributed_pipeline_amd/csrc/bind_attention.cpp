@@ -1,5 +1,6 @@
 // Bindings of the attention kernels: training forward / backward (attention.hip,
-// attention128.hip) and the KV-cache decode steps (attn_decode.hip, attn_decode_block.hip).
+// attention128.hip) and the KV-cache decode steps (attn_decode.hip, attn_decode_block.hip,
+// attn_decode_fp8.hip).
 #include "bind_util.h"
 
 static std::vector<at::Tensor> attn_fwd(const at::Tensor& qkv, int64_t heads, double p, bool causal,
@@ -196,6 +197,76 @@ static c10::optional<at::Tensor> attn_decode_block(const at::Tensor& qkv_new, at
   return out;
 }
 
+// The decode step over a one-byte cache (csrc/attn_decode_fp8.hip): qkv_new [B, 3 H D] bf16, k8 / v8 uint8
+// [B, H, Lmax, D], ke / ve int8 [B, H, Lmax] (all four updated in place at row lens[b]), lens [B] int32
+// -> out [B, H D] bf16, or None for a case the kernel does not cover: the caller's PyTorch path takes it.
+static c10::optional<at::Tensor> attn_decode_fp8(const at::Tensor& qkv_new, at::Tensor& k8, at::Tensor& ke,
+                                                 at::Tensor& v8, at::Tensor& ve, const at::Tensor& lens,
+                                                 int64_t n_heads) {
+  TORCH_CHECK(qkv_new.dim() == 2 && lens.dim() == 1 && n_heads > 0, "attn_decode_fp8: qkv_new [B, 3 H D], lens [B]");
+  const bool k_ok = fp8_cache_usable(k8, ke, qkv_new.device(), "attn_decode_fp8 (k)");
+  const bool v_ok = fp8_cache_usable(v8, ve, qkv_new.device(), "attn_decode_fp8 (v)");
+  const int64_t B = k8.size(0), H = k8.size(1), Lmax = k8.size(2), D = k8.size(3);
+  TORCH_CHECK(H == n_heads && v8.sizes() == k8.sizes() && qkv_new.size(0) == B && qkv_new.size(1) == 3 * H * D &&
+                  lens.size(0) == B,
+              "attn_decode_fp8: shapes of qkv_new, the caches, lens and n_heads do not agree");
+  TORCH_CHECK(lens.scalar_type() == at::kInt, "attn_decode_fp8: lens must be int32");
+  if (!k_ok || !v_ok || !qkv_new.is_cuda() || !lens.is_cuda() || lens.device() != qkv_new.device()) return c10::nullopt;
+  if (qkv_new.scalar_type() != at::kBFloat16 || !lens.is_contiguous()) return c10::nullopt;
+  if ((D != 64 && D != 128) || B == 0 || Lmax == 0 || Lmax > 0x7fffffffLL || B * H > 0x7fffffffLL) return c10::nullopt;
+  if (qkv_new.stride(1) != 1 || qkv_new.stride(0) % 8 != 0 || reinterpret_cast<uintptr_t>(qkv_new.data_ptr()) % 16 != 0)
+    return c10::nullopt;
+  const c10::DeviceGuard guard(qkv_new.device());
+  at::Tensor out = at::empty({B, H * D}, qkv_new.options());
+  const bool ok = dpa::launch_attn_decode_fp8(
+      bf_ptr(qkv_new), qkv_new.stride(0), k8.data_ptr<uint8_t>(), ke.data_ptr<int8_t>(), v8.data_ptr<uint8_t>(),
+      ve.data_ptr<int8_t>(), k8.stride(0), k8.stride(1), ke.stride(0), ke.stride(1), v8.stride(0), v8.stride(1),
+      ve.stride(0), ve.stride(1), lens.data_ptr<int>(), (int)B, (int)H, (int)Lmax, (int)D, bf_mut(out), cur_stream());
+  if (!ok) return c10::nullopt;
+  return out;
+}
+
+// The prefill's quantizing store: qkv [B, L, 3 H D] bf16 (last stride 1, any batch and position stride),
+// lens [B] int32; K and V of the positions l < lens[b] go to cache row l -> false for a case the kernel
+// does not cover (nothing written).
+static bool kv8_store(const at::Tensor& qkv, const at::Tensor& lens, at::Tensor& k8, at::Tensor& ke, at::Tensor& v8,
+                      at::Tensor& ve) {
+  TORCH_CHECK(qkv.dim() == 3 && lens.dim() == 1, "kv_store: qkv [B, L, 3 H D], lens [B]");
+  const bool k_ok = fp8_cache_usable(k8, ke, qkv.device(), "kv_store (k)");
+  const bool v_ok = fp8_cache_usable(v8, ve, qkv.device(), "kv_store (v)");
+  const int64_t B = k8.size(0), H = k8.size(1), Lmax = k8.size(2), D = k8.size(3), L = qkv.size(1);
+  TORCH_CHECK(v8.sizes() == k8.sizes() && qkv.size(0) == B && qkv.size(2) == 3 * H * D && lens.size(0) == B,
+              "kv_store: shapes of qkv, the caches and lens do not agree");
+  TORCH_CHECK(L <= Lmax, "kv_store: ", L, " positions do not fit a cache of ", Lmax);
+  TORCH_CHECK(lens.scalar_type() == at::kInt, "kv_store: lens must be int32");
+  if (!k_ok || !v_ok || !qkv.is_cuda() || !lens.is_cuda() || lens.device() != qkv.device()) return false;
+  if (qkv.scalar_type() != at::kBFloat16 || !lens.is_contiguous()) return false;
+  if ((D != 64 && D != 128) || B == 0 || L == 0 || B > 0x7fffffffLL || Lmax > 0x7fffffffLL) return false;
+  if (qkv.stride(2) != 1 || qkv.stride(0) % 8 != 0 || qkv.stride(1) % 8 != 0 ||
+      reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 != 0)
+    return false;
+  const c10::DeviceGuard guard(qkv.device());
+  return dpa::launch_kv8_store(bf_ptr(qkv), qkv.stride(0), qkv.stride(1), lens.data_ptr<int>(), k8.data_ptr<uint8_t>(),
+                               ke.data_ptr<int8_t>(), v8.data_ptr<uint8_t>(), ve.data_ptr<int8_t>(), k8.stride(0),
+                               k8.stride(1), ke.stride(0), ke.stride(1), v8.stride(0), v8.stride(1), ve.stride(0),
+                               ve.stride(1), (int)B, (int)L, (int)H, (int)Lmax, (int)D, cur_stream());
+}
+
+// x [R, D] bf16 -> (codes uint8 [R, D], exponents int8 [R]), or None for a case the kernel does not cover.
+static c10::optional<std::vector<at::Tensor>> kv8_quantize(const at::Tensor& x) {
+  TORCH_CHECK(x.dim() == 2, "kv_quantize: x must be [R, D]");
+  const int64_t R = x.size(0), D = x.size(1);
+  if (!x.is_cuda() || x.scalar_type() != at::kBFloat16 || !x.is_contiguous() || (D != 64 && D != 128) || R == 0 ||
+      reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 != 0)
+    return c10::nullopt;
+  const c10::DeviceGuard guard(x.device());
+  at::Tensor codes = at::empty({R, D}, x.options().dtype(at::kByte));
+  at::Tensor exps = at::empty({R}, x.options().dtype(at::kChar));
+  if (!dpa::launch_kv8_quantize(bf_ptr(x), R, (int)D, codes.data_ptr<uint8_t>(), exps.data_ptr<int8_t>(), cur_stream()))
+    return c10::nullopt;
+  return std::vector<at::Tensor>{codes, exps};
+}
+
 void dpa::register_attention(pybind11::module& m) {
   m.def("attn128_supports", &dpa::attn128_supports, "the persistent L = 128 attention covers (L, D, causal)");
   m.def("attn_fwd", &attn_fwd, "fused attention forward (head_dim 64/128) -> (out, lse)", py::arg("qkv"),
@@ -220,4 +291,14 @@ void dpa::register_attention(pybind11::module& m) {
         "KV-cache append + attention of a block of T <= 8 new tokens per row, as T successive attn_decode calls in one pass over the caches -> out [B, T, H D] bf16 | None (case not covered)",
         py::arg("qkv_new"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"), py::arg("n_heads"),
         py::arg("counts") = py::none());
+  m.def("attn_decode_fp8", &attn_decode_fp8,
+        "attn_decode over a one-byte cache (e4m3fn codes + one int8 exponent per row): quantizing append + single-query attention -> out [B, H D] bf16 | None (case not covered)",
+        py::arg("qkv_new"), py::arg("k8"), py::arg("ke"), py::arg("v8"), py::arg("ve"), py::arg("lens"),
+        py::arg("n_heads"));
+  m.def("kv8_store", &kv8_store,
+        "quantize K and V of qkv [B, L, 3 H D] bf16 into the one-byte cache for the positions below lens -> bool (False: case not covered, nothing written)",
+        py::arg("qkv"), py::arg("lens"), py::arg("k8"), py::arg("ke"), py::arg("v8"), py::arg("ve"));
+  m.def("kv8_quantize", &kv8_quantize,
+        "x [R, D] bf16 -> (codes uint8 [R, D], exponents int8 [R]) of the one-byte cache format | None (case not covered)",
+        py::arg("x"));
 }

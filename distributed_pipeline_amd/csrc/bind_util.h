@@ -56,6 +56,22 @@ static inline bool usable_acc(const c10::optional<at::Tensor>& t, int64_t numel,
          t->device() == dev;
 }
 
+// The one-byte K/V cache of csrc/attn_decode_fp8.hip: codes uint8 [B, H, Lmax, D] and exponents int8
+// [B, H, Lmax] (views into larger buffers work).  Wrong dtypes or shapes are refused; -> whether the
+// kernels can take the layout (packed rows of D bytes on 16 bytes, packed exponent rows, on `dev`).
+static inline bool fp8_cache_usable(const at::Tensor& codes, const at::Tensor& exps, const c10::Device& dev,
+                                    const char* name) {
+  TORCH_CHECK(codes.scalar_type() == at::kByte && exps.scalar_type() == at::kChar, name,
+              ": codes must be uint8 and exponents int8");
+  TORCH_CHECK(codes.dim() == 4 && exps.dim() == 3 && exps.size(0) == codes.size(0) && exps.size(1) == codes.size(1) &&
+                  exps.size(2) == codes.size(2),
+              name, ": codes must be [B, H, Lmax, D] and exponents [B, H, Lmax]");
+  if (!codes.is_cuda() || !exps.is_cuda() || codes.device() != dev || exps.device() != dev) return false;
+  const int64_t D = codes.size(3);
+  return codes.stride(3) == 1 && codes.stride(2) == D && codes.stride(0) % 16 == 0 && codes.stride(1) % 16 == 0 &&
+         reinterpret_cast<uintptr_t>(codes.data_ptr()) % 16 == 0 && (exps.stride(2) == 1 || exps.size(2) <= 1);
+}
+
 static inline void check_i64(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kLong && t.is_contiguous(), name,
               " must be a contiguous int64 HIP tensor");

@@ -233,6 +233,28 @@ bool launch_attn_decode_beam(const uint16_t* qkv_new, int64_t qkv_stride, uint16
                              const uint8_t* src, int64_t src_stride, int W, int B, int H, int Lmax, int D,
                              uint16_t* out, hipStream_t s);
 
+// ---- attn_decode_fp8.hip: the same step over a one-byte cache, and the quantizing stores ----------
+// The format (the file's header has it in full): a row of D values is D e4m3fn codes of x 2^-e and one
+// int8 exponent e = max(p - 9 + (m > 0.875), -127) from (m, p) = frexp(max |x|), 0 for a zero row.
+// Code rows of D bytes at base + b * sb + h * sh + key * D, exponents at ebase + b * esb + h * esh + key.
+// launch_attn_decode with K^, V^ for K, V: an active row quantizes its new k and v, stores codes and
+// exponents at cache row lens[b] and attends over the cached keys and the dequantized new one; an
+// inactive row stores nothing and returns zeros; rows at or beyond lens[b] are never read.  false, with
+// no launch: D not in {64, 128}, qkv_stride no multiple of 8 elements, a code stride no multiple of 16
+// bytes, a base that is not 16-byte aligned, an empty shape or a null pointer.
+bool launch_attn_decode_fp8(const uint16_t* qkv_new, int64_t qkv_stride, uint8_t* k8, int8_t* ke, uint8_t* v8,
+                            int8_t* ve, int64_t k_sb, int64_t k_sh, int64_t ke_sb, int64_t ke_sh, int64_t v_sb,
+                            int64_t v_sh, int64_t ve_sb, int64_t ve_sh, const int* lens, int B, int H, int Lmax, int D,
+                            uint16_t* out, hipStream_t s);
+// The prefill's store: K and V of qkv [B][L][3][H][D] bf16 (row b, position l at b * qkv_sb + l * qkv_sl
+// elements) quantized into cache row l for every l < lens[b]; nothing else is written.  false, with no
+// launch: as above, or L > Lmax.
+bool launch_kv8_store(const uint16_t* qkv, int64_t qkv_sb, int64_t qkv_sl, const int* lens, uint8_t* k8, int8_t* ke,
+                      uint8_t* v8, int8_t* ve, int64_t k_sb, int64_t k_sh, int64_t ke_sb, int64_t ke_sh, int64_t v_sb,
+                      int64_t v_sh, int64_t ve_sb, int64_t ve_sh, int B, int L, int H, int Lmax, int D, hipStream_t s);
+// x [rows][D] bf16, packed -> codes [rows][D], exps [rows].
+bool launch_kv8_quantize(const uint16_t* x, int64_t rows, int D, uint8_t* codes, int8_t* exps, hipStream_t s);
+
 // ---- attn_decode_block.hip: the same step for a block of T new tokens per row (lookahead decoding) ----
 // qkv_new [B][T][3][H][D] bf16 (row b, token j at b * qkv_sb + j * qkv_st elements), counts [B] int32
 // or null (= T), out [B][T][H][D] bf16.  With c_b = 0 for lens[b] outside [0, Lmax) and otherwise

@@ -77,8 +77,13 @@ class GPT2LMModel(nn.Module):
 
     # ---- generation: K/V cache, prefill, one-token decode steps (inference only) ----------
 
-    def init_cache(self, batch, max_len, device=None, dtype=None):
-        """An empty cache for ``batch`` rows of up to ``max_len`` tokens (prompt + continuation)."""
+    def init_cache(self, batch, max_len, device=None, dtype=None, kv_dtype="bf16"):
+        """An empty cache for ``batch`` rows of up to ``max_len`` tokens (prompt + continuation).
+        ``kv_dtype="fp8"``: the one-byte cache of ``ops.decode`` - e4m3fn codes and one int8 exponent per
+        cached row - for :meth:`prefill`, :meth:`decode_step` and :meth:`generate`; ``"bf16"`` (the
+        default) stores the values in ``dtype`` (the compute dtype)."""
+        if kv_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}")
         cfg = self.cfg
         if not 1 <= max_len <= cfg["max_position_embeddings"]:
             raise ValueError(f"max_len {max_len} outside 1 .. max_position_embeddings "
@@ -86,7 +91,7 @@ class GPT2LMModel(nn.Module):
         device = self.wte.weight.device if device is None else device
         dtype = self.compute_dtype if dtype is None else dtype
         return KVCache(len(self.h), batch, cfg["num_heads"], max_len, cfg["hidden_size"] // cfg["num_heads"],
-                       device, dtype)
+                       device, dtype, kv_dtype=kv_dtype)
 
     def _blocks(self, x, a, attend):
         """The block stack of ``hidden_states`` in eval mode with ``attend(i, qkv)`` as layer i's
@@ -103,8 +108,9 @@ class GPT2LMModel(nn.Module):
     def prefill(self, input_ids, lens, cache):
         """Right-padded prompts ``input_ids`` [B, Lp] of ``1 <= lens[b] <= Lp`` tokens: one causal
         forward (what stands behind a row's prompt never reaches it), each layer's K and V of the
-        prompt positions copied into ``cache``, ``cache.lens = lens`` -> the logits [B, V] at each
-        row's last prompt position."""
+        prompt positions copied into ``cache`` (quantized into an fp8 cache; the prompt's own forward
+        attends over the unquantized values), ``cache.lens = lens`` -> the logits [B, V] at each row's
+        last prompt position."""
         dt = self.compute_dtype
         B, Lp = input_ids.shape
         if Lp > cache.max_len or B != cache.batch:
@@ -117,8 +123,13 @@ class GPT2LMModel(nn.Module):
             input_ids = torch.nn.functional.pad(input_ids, (0, L - Lp))
         heads, D = cache.heads, cache.head_dim
         inside = (torch.arange(Lp, device=input_ids.device).view(1, Lp) < lens.view(B, 1)).view(B, 1, Lp, 1)
+        if cache.fp8:
+            from ..ops.decode import kv_store
 
         def attend(i, qkv):
+            if cache.fp8:  # one quantizing store per layer; positions at or beyond lens stay untouched
+                kv_store(qkv.view(B, L, -1)[:, :Lp], lens, cache.k[i], cache.ke[i], cache.v[i], cache.ve[i])
+                return ops.attention(qkv, heads, 0.0, True, False)
             kv = qkv.view(B, L, 3, heads, D)[:, :Lp].permute(2, 0, 3, 1, 4)  # [3, B, H, Lp, D]
             for dst, src in ((cache.k[i], kv[1]), (cache.v[i], kv[2])):
                 dst[:, :, :Lp] = torch.where(inside, src.to(dst.dtype), dst[:, :, :Lp])
@@ -138,8 +149,11 @@ class GPT2LMModel(nn.Module):
         ``cache.lens`` advances on the device.  A parked row (``lens`` outside 0 .. max_len - 1)
         does no cache work, keeps its ``lens``, and its logits mean nothing.  ``table``: a pair
         ``(src uint8 [B, max_len], beams)`` handed to ``attention_decode`` - the rows are groups
-        of ``beams`` slots that read their cached keys through ``src`` (beam search)."""
-        from ..ops.decode import attention_decode
+        of ``beams`` slots that read their cached keys through ``src`` (beam search; not over an
+        fp8 cache).  Over an fp8 cache the step is ``ops.decode.attention_decode_fp8``."""
+        from ..ops.decode import attention_decode, attention_decode_fp8
+        if cache.fp8 and table is not None:
+            raise ValueError("an fp8 cache has no indirection-table variant: beam search needs kv_dtype='bf16'")
         dt = self.compute_dtype
         B = tokens.shape[0]
         heads = cache.heads
@@ -153,6 +167,9 @@ class GPT2LMModel(nn.Module):
         kw = {} if table is None else {"src": table[0], "beams": table[1]}
 
         def attend(i, qkv):
+            if cache.fp8:
+                return attention_decode_fp8(qkv.view(B, -1), cache.k[i], cache.ke[i], cache.v[i], cache.ve[i],
+                                            cache.lens, heads).view(1, B, -1)
             return attention_decode(qkv.view(B, -1), cache.k[i], cache.v[i], cache.lens, heads, **kw).view(1, B, -1)
 
         a = self._blocks(x, a, attend)
@@ -163,7 +180,7 @@ class GPT2LMModel(nn.Module):
     def generate(self, input_ids, lens, max_new_tokens, *, temperature=1.0, top_k=0, top_p=0.0, eos_id=None,
                  generator=None, cache=None, check_every=16, noise_seed=None, row_base=0, repetition_penalty=1.0,
                  presence_penalty=0.0, frequency_penalty=0.0, no_repeat_ngram=0, min_new_tokens=0,
-                 penalize_prompt=True, return_logprobs=False):
+                 penalize_prompt=True, return_logprobs=False, kv_dtype=None):
         """Continue right-padded prompts -> (tokens [B, max_new_tokens], new_lens [B]).
 
         ``temperature == 0`` is greedy (ties to the lowest id); otherwise ``logits / temperature``,
@@ -175,6 +192,9 @@ class GPT2LMModel(nn.Module):
         further cache work) and the rest of its output row is ``eos_id`` (0 without one).
         ``new_lens[b]`` counts the tokens the row really produced, a closing ``eos_id`` included.
         ``cache``: one from :meth:`init_cache` to use (default: a new one of just the size needed).
+        ``kv_dtype``: "bf16" or "fp8" - the one-byte cache, half the bytes per cached token - for
+        the new cache (default "bf16"); given together with a ``cache`` of the other kind it is an
+        error.
         The loop runs on the device; the host looks at it once every ``check_every`` steps (0:
         never), to stop early when every row has finished.
 
@@ -198,8 +218,14 @@ class GPT2LMModel(nn.Module):
         philox = noise_seed is not None and temperature > 0
         B, Lp = input_ids.shape
         dev = input_ids.device
+        if kv_dtype not in (None, "bf16", "fp8"):
+            raise ValueError(f"kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}")
         if cache is None:
-            cache = self.init_cache(B, min(Lp + max_new_tokens, self.cfg["max_position_embeddings"]), dev)
+            cache = self.init_cache(B, min(Lp + max_new_tokens, self.cfg["max_position_embeddings"]), dev,
+                                    **({"kv_dtype": "fp8"} if kv_dtype == "fp8" else {}))
+        elif kv_dtype is not None and (kv_dtype == "fp8") != cache.fp8:
+            raise ValueError(f"kv_dtype={kv_dtype!r} contradicts the given cache, which is "
+                             f"{'fp8' if cache.fp8 else 'bf16'}")
         fill = 0 if eos_id is None else int(eos_id)
         out = torch.full((B, max_new_tokens), fill, dtype=torch.long, device=dev)
         new_lens = torch.zeros(B, dtype=torch.long, device=dev)
@@ -331,6 +357,8 @@ class GPT2LMModel(nn.Module):
         caller commits as many positions as it accepted, and what was stored beyond them is
         overwritten or never read."""
         from ..ops.decode import attention_decode_block
+        if cache.fp8:
+            raise ValueError("decode_block has no fp8 variant: lookahead decoding needs kv_dtype='bf16'")
         dt = self.compute_dtype
         B, T = tokens.shape
         heads = cache.heads
@@ -395,6 +423,8 @@ class GPT2LMModel(nn.Module):
         dev = input_ids.device
         if cache is None:
             cache = self.init_cache(B, min(Lp + N, self.cfg["max_position_embeddings"]), dev)
+        elif cache.fp8:
+            raise ValueError("generate_lookahead needs a bf16 cache: the block decode kernel has no fp8 variant")
         max_len = cache.max_len
         fill = 0 if eos_id is None else int(eos_id)
         # T spare columns behind both: where the masked-out slots of a block are written
@@ -501,6 +531,8 @@ class GPT2LMModel(nn.Module):
         T = int(max_new_tokens)
         if cache is None:
             cache = self.init_cache(B * W, min(Lp + T, self.cfg["max_position_embeddings"]), dev)
+        elif cache.fp8:
+            raise ValueError("beam_search needs a bf16 cache: the table decode kernel has no fp8 variant")
         elif cache.batch != B * W:
             raise ValueError(f"beam search over {B} prompts x {W} beams needs a cache of {B * W} rows, "
                              f"got {cache.batch}")
@@ -585,11 +617,23 @@ class GPT2LMModel(nn.Module):
 class KVCache:
     """Per-layer K / V of shape [B, H, max_len, D] - views into one buffer - and ``lens`` int32
     [B], the tokens cached per row (outside 0 .. max_len - 1: a parked row).  ``table``: after a
-    beam search, the uint8 [B / W, W, max_len] indirection table of its last decode step."""
+    beam search, the uint8 [B / W, W, max_len] indirection table of its last decode step.
 
-    def __init__(self, layers, batch, heads, max_len, head_dim, device, dtype):
+    ``kv_dtype="fp8"`` (``fp8`` is then True): ``buf`` holds uint8 e4m3fn codes [layers, 2, B, H,
+    max_len, D] and ``ebuf`` int8 exponents [layers, 2, B, H, max_len], one per cached row
+    (``ops.decode`` has the format); ``k`` / ``v`` are the code views and ``ke`` / ``ve`` the exponent
+    views.  Half the bytes per cached token, plus one per row."""
+
+    def __init__(self, layers, batch, heads, max_len, head_dim, device, dtype, kv_dtype="bf16"):
         self.batch, self.heads, self.max_len, self.head_dim = batch, heads, max_len, head_dim
-        self.buf = torch.zeros(layers, 2, batch, heads, max_len, head_dim, device=device, dtype=dtype)
+        self.fp8 = kv_dtype == "fp8"
+        if self.fp8:
+            self.buf = torch.zeros(layers, 2, batch, heads, max_len, head_dim, device=device, dtype=torch.uint8)
+            self.ebuf = torch.zeros(layers, 2, batch, heads, max_len, device=device, dtype=torch.int8)
+            self.ke = [self.ebuf[i, 0] for i in range(layers)]
+            self.ve = [self.ebuf[i, 1] for i in range(layers)]
+        else:
+            self.buf = torch.zeros(layers, 2, batch, heads, max_len, head_dim, device=device, dtype=dtype)
         self.k = [self.buf[i, 0] for i in range(layers)]
         self.v = [self.buf[i, 1] for i in range(layers)]
         self.lens = torch.zeros(batch, dtype=torch.int32, device=device)
@@ -603,9 +647,14 @@ class KVCache:
             raise ValueError(f"{self.batch} cache rows are not whole groups of {beams}")
         view = KVCache.__new__(KVCache)
         view.batch, view.heads, view.max_len, view.head_dim = self.batch // beams, self.heads, self.max_len, self.head_dim
+        view.fp8 = self.fp8
         view.buf = self.buf[:, :, slot::beams]
         view.k = [k[slot::beams] for k in self.k]
         view.v = [v[slot::beams] for v in self.v]
+        if self.fp8:
+            view.ebuf = self.ebuf[:, :, slot::beams]
+            view.ke = [e[slot::beams] for e in self.ke]
+            view.ve = [e[slot::beams] for e in self.ve]
         view.lens = self.lens[slot::beams]
         view.table = None
         return view

@@ -38,6 +38,36 @@ row of the same call appends to; this holds whenever the active rows of a group 
 which is what beam search guarantees.  Re-parenting W hypotheses then rewrites ``W Lmax`` bytes per
 prompt instead of gathering ``[layers, 2, B W, H, Lmax, D]`` into a second buffer.
 
+The one-byte cache: ``kv_quantize``, ``kv_store``, ``attention_decode_fp8``
+---------------------------------------------------------------------------
+A cached row - the D values of one (K or V, batch row, head, position) - is stored as D OCP
+``e4m3fn`` codes (uint8) and one int8 exponent ``e``.  For a row ``x`` of finite values and
+``a = max|x_i|``: ``e = 0`` if ``a == 0``; otherwise ``(m, p) = frexp(a)``, m in [0.5, 1), and
+``e = max(p - 9 + (1 if m > 0.875 else 0), -127)``.  Then ``a * 2^-e`` lies in (224, 448] - 448 =
+0.875 * 2^9 is e4m3fn's largest finite value - so no element saturates.  ``code_i = e4m3fn(x_i * 2^-e)``,
+round to nearest even, subnormals kept; ``x^_i = float(code_i) * 2^e``.  The scaling is by a power of
+two, so codes and exponent are a function of the input bits alone: the kernels and PyTorch
+(``torch.ldexp(x.float(), -e).to(torch.float8_e4m3fn)``) agree bit for bit.  Non-finite values: memory
+safe, the stored bytes are unspecified.  One finite edge: a row maximum above 240 * 2^120 (the top
+eight bf16 magnitudes) rounds up to the code 256 at e = 120, and 2^128 dequantizes to inf in fp32.
+
+* ``kv_quantize(x [..., D]) -> (codes uint8 [..., D], exp int8 [...])``; ``kv_dequantize(codes, exp) ->
+  fp32 [..., D]``, exact.
+* ``kv_store(qkv [B, L, 3*H*D], lens int32 [B], k8, ke, v8, ve)``: the prefill's store.  K and V of the
+  positions ``l < lens[b]`` are quantized into cache row l of ``k8`` / ``v8`` uint8 [B, H, Lmax, D] and
+  ``ke`` / ``ve`` int8 [B, H, Lmax]; every other byte is left as it is.
+* ``attention_decode_fp8(qkv_new, k8, ke, v8, ve, lens, n_heads)`` is ``attention_decode`` with the
+  dequantized caches in place of K and V: an active row quantizes its new k and v, stores codes and
+  exponents at row ``lens[b]`` and attends over the cached keys and its own **dequantized** new key and
+  value - "append, then attend over the cache" is one definition whatever the step.  An inactive row
+  stores nothing, codes and exponents included, and returns zeros; rows at or beyond ``lens[b]`` are
+  never read, whatever they hold.
+
+bf16 on a HIP device with D in {64, 128} and packed 16-byte code rows: csrc/attn_decode_fp8.hip (the
+conversions are gfx950's ``v_cvt_pk_fp8_f32`` / ``v_cvt_pk_f32_fp8``; the exponents are applied once per
+key, as exact ``ldexp``).  Anything else: the ``_ref`` twins in PyTorch.  There is no table (beam) and no
+block (lookahead) variant.
+
 Attention of a block of new tokens: ``attention_decode_block``
 --------------------------------------------------------------
 ``attention_decode_block(qkv_new [B, T, 3*H*D], k_cache, v_cache, lens int32 [B], n_heads, *,
@@ -293,6 +323,147 @@ def attention_decode(qkv_new, k_cache, v_cache, lens, n_heads, *, src=None, beam
             if out is not None:
                 return out
     return attention_decode_ref(qkv_new, k_cache, v_cache, lens, n_heads, src=src, beams=beams)
+
+
+# ---- the one-byte cache: kv_quantize, kv_store, attention_decode_fp8 ---------------------------------
+
+def kv_quantize_ref(x):
+    """The format's definition in PyTorch (any device, any float dtype) -> (codes uint8 [..., D], exp
+    int8 [...]).  Non-finite values: unspecified.
+
+    The codes are ``torch.ldexp(x.float(), -e).to(torch.float8_e4m3fn)`` with every step exact on any
+    device: the exponent is read off the bits of the largest magnitude (what ``frexp`` returns, without
+    its arithmetic), ``2^-e`` is assembled from its bits, and a subnormal fp32 element is scaled from
+    its integer mantissa, so a device whose PyTorch kernels flush fp32 subnormals to zero or round
+    ``pow(2, k)`` gives the same bytes."""
+    xf = x.detach().float().contiguous()
+    mag = xf.view(torch.int32) & 0x7FFFFFFF
+    amax = mag.amax(-1)  # integer order is magnitude order
+    E, M = amax >> 23, amax & 0x7FFFFF
+    # a normal a = 1.f 2^(E - 127) has frexp (1.f / 2, E - 126); m > 0.875 is f > 0.75; a subnormal a lies
+    # below the clamp
+    e = (E - 135 + (M > 0x600000).to(E.dtype)).clamp(min=-127)
+    e = torch.where(amax == 0, torch.zeros_like(e), e)
+    # 2^-e = 2^-120 .. 2^127 assembled from its bits: exact on every device (a device's powf need not be)
+    scale = ((127 - e) << 23).view(torch.float32).unsqueeze(-1)
+    scaled = xf * scale
+    # a subnormal element M 2^-149, through normal intermediates only (an underflow to 0 rounds to 0 anyway)
+    sub = torch.copysign((mag & 0x7FFFFF).float() * 2.0 ** -75 * scale * 2.0 ** -74, xf)
+    codes = torch.where(mag >> 23 == 0, sub, scaled).to(torch.float8_e4m3fn).view(torch.uint8)
+    return codes.view(x.shape), e.to(torch.int8)
+
+
+def kv_dequantize(codes, exp):
+    """-> fp32 [..., D]: ``float(code) * 2^exp``, exact, assembled from the bits so that a result
+    below 2^-126 is the subnormal it should be on any device (2^128, the one overflow, is inf)."""
+    f = codes.contiguous().view(torch.float8_e4m3fn).float()  # exact: zero, or a normal fp32 of 4 significant bits
+    bits = f.view(torch.int32)
+    e = exp.to(torch.int32).unsqueeze(-1)
+    sign, mag = bits & -0x80000000, bits & 0x7FFFFFFF
+    En = (mag >> 23) + e  # the result's exponent field
+    normal = mag + (e << 23)
+    shift = (1 - En).clamp(0, 31)
+    denorm = ((mag & 0x7FFFFF) | 0x800000) >> shift  # exact: the 4 significant bits stay above bit 9
+    out = torch.where(En >= 1, normal, denorm)
+    out = torch.where(En >= 255, torch.full_like(out, 0x7F800000), out)
+    out = torch.where((mag == 0) | (mag > 0x7F800000), mag, out)  # zero and NaN codes stay what they are
+    return (out | sign).view(torch.float32).view(codes.shape)
+
+
+@torch.no_grad()
+def kv_quantize(x):
+    """-> (codes uint8 [..., D], exp int8 [...]): the module docstring has the format."""
+    if x.is_cuda:
+        ext = get_ext()  # raises on a GPU without the built extension: no quiet fall-back
+        if ext is not None and x.dtype == torch.bfloat16 and x.numel() > 0:
+            D = x.shape[-1]
+            out = ext.kv8_quantize(x.detach().reshape(-1, D).contiguous())
+            if out is not None:
+                return out[0].view(x.shape), out[1].view(x.shape[:-1])
+    return kv_quantize_ref(x)
+
+
+def _check_fp8_cache(k8, ke, v8, ve):
+    if k8.dim() != 4 or k8.shape != v8.shape or ke.shape != k8.shape[:3] or ve.shape != k8.shape[:3]:
+        raise ValueError(f"codes must be [B, H, Lmax, D] and exponents [B, H, Lmax], got {tuple(k8.shape)}, "
+                         f"{tuple(ke.shape)}, {tuple(v8.shape)}, {tuple(ve.shape)}")
+    if k8.dtype != torch.uint8 or v8.dtype != torch.uint8 or ke.dtype != torch.int8 or ve.dtype != torch.int8:
+        raise ValueError(f"codes must be uint8 and exponents int8, got {k8.dtype}, {ke.dtype}, {v8.dtype}, {ve.dtype}")
+
+
+def kv_store_ref(qkv, lens, k8, ke, v8, ve):
+    """The prefill's store in PyTorch (any device, any float dtype): a position at or beyond ``lens[b]``
+    writes back what its slot already holds."""
+    _check_fp8_cache(k8, ke, v8, ve)
+    B, H, Lmax, D = k8.shape
+    L = qkv.shape[1]
+    if qkv.shape[0] != B or qkv.shape[2] != 3 * H * D or tuple(lens.shape) != (B,) or L > Lmax:
+        raise ValueError(f"qkv {tuple(qkv.shape)} and lens {tuple(lens.shape)} do not fit caches {tuple(k8.shape)}")
+    kv = qkv.detach().reshape(B, L, 3, H, D)
+    inside = torch.arange(L, device=qkv.device).view(1, L) < lens.to(qkv.device).view(B, 1)
+    for c8, ce, part in ((k8, ke, kv[:, :, 1]), (v8, ve, kv[:, :, 2])):
+        codes, ex = kv_quantize_ref(part)  # [B, L, H, D], [B, L, H]
+        c8[:, :, :L] = torch.where(inside.view(B, 1, L, 1), codes.permute(0, 2, 1, 3), c8[:, :, :L])
+        ce[:, :, :L] = torch.where(inside.view(B, 1, L), ex.permute(0, 2, 1), ce[:, :, :L])
+
+
+@torch.no_grad()
+def kv_store(qkv, lens, k8, ke, v8, ve):
+    """Quantize K and V of ``qkv`` [B, L, 3*H*D] into the caches for the positions below ``lens``, in
+    place: the module docstring has the definition."""
+    _check_fp8_cache(k8, ke, v8, ve)
+    if qkv.is_cuda:
+        ext = get_ext()  # raises on a GPU without the built extension: no quiet fall-back
+        if ext is not None and qkv.dim() == 3:
+            x = qkv
+            if x.stride(-1) != 1 or x.stride(0) % 8 or x.stride(1) % 8 or x.data_ptr() % 16:
+                x = x.contiguous()
+            if ext.kv8_store(x, lens, k8, ke, v8, ve):
+                return
+    kv_store_ref(qkv, lens, k8, ke, v8, ve)
+
+
+def attention_decode_fp8_ref(qkv_new, k8, ke, v8, ve, lens, n_heads):
+    """The definition in fp32 PyTorch (any device, any float dtype); also the numerics yardstick of the
+    kernel's tests."""
+    _check_fp8_cache(k8, ke, v8, ve)
+    B, H, Lmax, D = k8.shape
+    assert H == n_heads and qkv_new.shape == (B, 3 * H * D) and lens.shape == (B,)
+    q, k, v = qkv_new.detach().reshape(B, 3, H, D).unbind(1)
+    n = lens.long()
+    active = (n >= 0) & (n < Lmax)
+    at = n.clamp(0, Lmax - 1)
+    rows = torch.arange(B, device=qkv_new.device)
+    # the append: an inactive row writes back what its slot already holds
+    for c8, ce, new in ((k8, ke, k), (v8, ve, v)):
+        codes, ex = kv_quantize_ref(new)
+        c8[rows, :, at] = torch.where(active.view(B, 1, 1), codes, c8[rows, :, at])
+        ce[rows, :, at] = torch.where(active.view(B, 1), ex, ce[rows, :, at])
+    pos = torch.arange(Lmax, device=qkv_new.device).view(1, Lmax)
+    mask = (pos <= at.view(B, 1)).view(B, 1, Lmax)
+    # what lies beyond lens - any byte, a NaN code, a wild exponent - must not reach a sum
+    kf = torch.where(mask.unsqueeze(-1), kv_dequantize(k8, ke), 0.0)
+    vf = torch.where(mask.unsqueeze(-1), kv_dequantize(v8, ve), 0.0)
+    s = torch.einsum("bhd,bhld->bhl", q.float(), kf) / math.sqrt(D)
+    p = torch.softmax(s.masked_fill(~mask, float("-inf")), -1)
+    o = torch.einsum("bhl,bhld->bhd", p, vf)
+    return torch.where(active.view(B, 1, 1), o, 0.0).to(qkv_new.dtype).reshape(B, H * D)
+
+
+@torch.no_grad()
+def attention_decode_fp8(qkv_new, k8, ke, v8, ve, lens, n_heads):
+    """-> out [B, H*D] in ``qkv_new``'s dtype; the four cache tensors updated in place.  The module
+    docstring has the definition."""
+    _check_fp8_cache(k8, ke, v8, ve)
+    if qkv_new.is_cuda:
+        ext = get_ext()  # raises on a GPU without the built extension: no quiet fall-back
+        if ext is not None:
+            if qkv_new.stride(-1) != 1 or qkv_new.stride(0) % 8 or qkv_new.data_ptr() % 16:
+                qkv_new = qkv_new.contiguous()
+            out = ext.attn_decode_fp8(qkv_new, k8, ke, v8, ve, lens, int(n_heads))
+            if out is not None:
+                return out
+    return attention_decode_fp8_ref(qkv_new, k8, ke, v8, ve, lens, n_heads)
 
 
 # ---- attention_decode_block, lookup_draft (lookahead decoding) -----------------------------------

@@ -35,6 +35,12 @@ for the first M tokens.  They combine with sampling, ``--noise philox`` and ``--
 under its step's logits after the penalties and before temperature, ``--top_k`` and ``--top_p``
 (``GPT2LMModel.generate(return_logprobs=True)``; ``python -m run.score --path`` gives the same numbers from a
 teacher-forced forward when no penalty is set).  It excludes ``--num_beams > 1`` and ``--lookahead``.
+
+``--kv_dtype fp8`` keeps the K/V cache in one byte per element - OCP e4m3fn codes and one power-of-two
+exponent per cached row (``ops.decode`` has the format): half the cache memory and half the bytes every
+decode step reads.  Its continuations are those of a slightly different model, not bf16's bit for bit.
+It combines with sampling, ``--noise philox``, the penalties and ``--logprobs`` and excludes
+``--num_beams > 1`` and ``--lookahead``.  The default is ``bf16``.
 """
 import json
 import os
@@ -110,7 +116,8 @@ def main(namespace):
                 res = model.generate(ids[:, :Lp].contiguous(), lens, Ln, temperature=args.temperature,
                                      top_k=args.top_k, top_p=args.top_p, eos_id=eos, generator=gen,
                                      noise_seed=args.seed if args.noise == "philox" else None, row_base=n,
-                                     **args.logit_processors(), **({"return_logprobs": True} if args.logprobs else {}))
+                                     **args.logit_processors(), **({"return_logprobs": True} if args.logprobs else {}),
+                                     **({"kv_dtype": args.kv_dtype} if args.kv_dtype != "bf16" else {}))
                 toks, new_lens = res[:2]
                 if args.logprobs:
                     logprobs = res[2].cpu()

@@ -1,7 +1,11 @@
 """Time the attention of one GPT-2 decode step: the fused kernel (csrc/attn_decode.hip through
 ``ext.attn_decode``) against the PyTorch path of ``ops.decode.attention_decode`` on the same
 tensors, and against a device copy of as many bytes as the step has to read from the K/V caches
-(2 * len * D * 2 bytes per (row, head)) - the bandwidth yardstick, measured in the same run.
+(2 * len * D * 2 bytes per (row, head)) - the bandwidth yardstick, measured in the same run.  Beside
+it, in the same interleaved run and at the same shapes, the step over the one-byte cache
+(csrc/attn_decode_fp8.hip through ``ext.attn_decode_fp8``) with yardsticks of its own: the bf16 kernel,
+and a device copy of the bytes the fp8 step reads (2 * len * (D + 1) per (row, head): codes and one
+exponent per row).
 
     python tools/attn_decode_bench.py [--B 64,8] [--lens 128,512,1023] [--H 12] [--D 64] [--reps 7] [--spread_mb 768]
                                         [--out FILE]
@@ -66,10 +70,21 @@ def shape(B, H, D, Lmax, n, reps, spread_bytes):
     lens = torch.full((B,), n, dtype=torch.int32, device="cuda")
     src = [torch.empty(nbytes, dtype=torch.uint8, device="cuda").random_() for _ in range(nsets)]
     dst = [torch.empty_like(t) for t in src]
-    turn = {"kernel": 0, "torch": 0, "copy": 0}
+    # the one-byte cache: finite codes of either sign (0x7f / 0xff are NaN), exponents around 2^-8
+    nbytes8 = 2 * n * (D + 1) * B * H
+    nsets8 = max(1, -(-spread_bytes // nbytes8))
+    codes = [torch.empty(2, B, H, Lmax, D, device="cuda", dtype=torch.uint8).random_(0, 0x7F, generator=g)
+             + 128 * torch.empty(2, B, H, Lmax, D, device="cuda", dtype=torch.uint8).random_(0, 2, generator=g)
+             for _ in range(nsets8)]
+    exps = [torch.empty(2, B, H, Lmax, device="cuda", dtype=torch.int8).random_(-10, -6, generator=g)
+            for _ in range(nsets8)]
+    src8 = [torch.empty(nbytes8, dtype=torch.uint8, device="cuda").random_() for _ in range(nsets8)]
+    dst8 = [torch.empty_like(t) for t in src8]
+    turn = {"kernel": 0, "torch": 0, "copy": 0, "kernel_fp8": 0, "copy_fp8": 0}
+    count = {"kernel_fp8": nsets8, "copy_fp8": nsets8}
 
     def nxt(name):
-        turn[name] = (turn[name] + 1) % nsets
+        turn[name] = (turn[name] + 1) % count.get(name, nsets)
         return turn[name]
 
     def kernel():
@@ -84,13 +99,28 @@ def shape(B, H, D, Lmax, n, reps, spread_bytes):
         i = nxt("copy")
         return dst[i].copy_(src[i])
 
-    out = interleaved({"kernel": (kernel, 2000), "torch": (torch_path, 50), "copy": (copy, 2000)}, reps)
+    def kernel_fp8():
+        i = nxt("kernel_fp8")
+        return ext.attn_decode_fp8(qkv, codes[i][0], exps[i][0], codes[i][1], exps[i][1], lens, H)
+
+    def copy_fp8():
+        i = nxt("copy_fp8")
+        return dst8[i].copy_(src8[i])
+
+    assert kernel_fp8() is not None, "the fp8 kernel must take this shape"
+    out = interleaved({"kernel": (kernel, 2000), "kernel_fp8": (kernel_fp8, 2000), "torch": (torch_path, 50),
+                       "copy": (copy, 2000), "copy_fp8": (copy_fp8, 2000)}, reps)
     for name in ("kernel", "torch", "copy"):
         out[name]["GBps"] = round(nbytes / out[name]["median_ms"] / 1e6, 1)
+    for name in ("kernel_fp8", "copy_fp8"):
+        out[name]["GBps"] = round(nbytes8 / out[name]["median_ms"] / 1e6, 1)
+    out["kernel_fp8"]["fraction_of_copy_rate"] = round(out["copy_fp8"]["median_ms"] / out["kernel_fp8"]["median_ms"], 3)
+    out["kernel_fp8"]["speedup_vs_bf16_kernel"] = round(out["kernel"]["median_ms"] / out["kernel_fp8"]["median_ms"], 3)
     # the copy's rate counts each byte once, though it reads and writes it
     out["kernel"]["fraction_of_copy_rate"] = round(out["copy"]["median_ms"] / out["kernel"]["median_ms"], 3)
     out["kernel"]["speedup_vs_torch"] = round(out["torch"]["median_ms"] / out["kernel"]["median_ms"], 2)
-    return {"B": B, "H": H, "D": D, "Lmax": Lmax, "len": n, "kv_bytes": nbytes, "cache_sets": nsets, **out}
+    return {"B": B, "H": H, "D": D, "Lmax": Lmax, "len": n, "kv_bytes": nbytes, "cache_sets": nsets,
+            "kv_bytes_fp8": nbytes8, "cache_sets_fp8": nsets8, **out}
 
 
 def model_step(B, n, reps):
