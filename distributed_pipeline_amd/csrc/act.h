@@ -4,6 +4,10 @@
 // Abramowitz-Stegun 7.1.26 rational approximation of erf (|error| < 1.5e-7,
 // far below bf16 resolution): one v_exp_f32 and one v_rcp_f32 instead of the
 // libm erff, and the same exp(-z^2/2) term serves the derivative's pdf.
+// SiLU z * rcp(1 + exp(-z)) and its derivative: one v_exp_f32, one v_rcp_f32 and three fp32
+// roundings, relative error < 4 * 2^-23.  v_rcp_f32 returns 0 for a result below the smallest
+// normal fp32, so the sigmoid is 0 for z < -87.34 (true value < 2^-126): there the absolute error
+// is below |z| * 2^-126 (the derivative's: (1 + |z|) * 2^-126).
 // Codes: 0 none, 1 gelu, 2 tanh, 3 silu; 4 = "the saved operand already IS act'(z)"
 // (forward epilogues that store the derivative instead of the pre-activation, so the
 // backward epilogue is one multiply instead of a second erf/exp evaluation).
