@@ -81,6 +81,12 @@ class ContinueSettings(S):
         = _("bf16", "Storage of the K/V cache. fp8: one byte per element (OCP e4m3fn codes and one power-of-two "
                     "exponent per cached row), half the memory and half the bytes a decode step reads; the "
                     "continuations can differ from bf16's. Excludes --num_beams > 1 and --lookahead.")
+    decode_linears: Choice("tile", "rows") \
+        = _("tile", "How the Linears of the decode steps run. tile: through the training GEMM, the rows padded into "
+                    "its tiles. rows: through the weight-streaming row kernel (ops.decode.linear_rows), one launch "
+                    "per Linear and the tied head included, where a step has at most 128 rows; an output row is "
+                    "then a function of its input row alone. The two round differently, so continuations can "
+                    "differ.")
     out_path: str \
         = _("", "Output .jsonl file (default: generated_<checkpoint>_seed<seed>.jsonl next to the checkpoint).")
     precision: Choice("bf16", "fp32") \
@@ -127,6 +133,8 @@ class GenerateSettings(
             raise ValueError(f"--noise must be torch or philox, got {self.noise!r}")
         if self.kv_dtype not in ("bf16", "fp8"):
             raise ValueError(f"--kv_dtype must be bf16 or fp8, got {self.kv_dtype!r}")
+        if self.decode_linears not in ("tile", "rows"):
+            raise ValueError(f"--decode_linears must be tile or rows, got {self.decode_linears!r}")
         if self.kv_dtype == "fp8" and (self.num_beams > 1 or self.lookahead > 0):
             raise ValueError("--kv_dtype fp8 is served by generate's own loop: the table (--num_beams > 1) and "
                              "block (--lookahead) decode kernels have no fp8 variant")

@@ -29,6 +29,9 @@ ARCH = os.environ.get("DPA_OFFLOAD_ARCH", "gfx950")
 EXT_NAME = "_C"
 COMMON = ["-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-D__HIP_PLATFORM_AMD__=1",
           "-Wno-unused-result", "-Wno-unused-command-line-argument"]  # every TU, before its -O flags
+# Flags of single kernel TUs.  linear_rows.hip is built without the packed-fp32 VALU forms (v_pk_add_f32,
+# v_pk_mul_f32, v_pk_fma_f32): its row contract is a bit-for-bit one and its epilogue needs none of them.
+TU_FLAGS = {"linear_rows.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _hipcc():
@@ -102,7 +105,7 @@ def build(force=False, jobs=None, debug=False, verbose=True):
     jobs_todo = []
     objects = []
     for src in kernels + host:
-        flags = bind if src in host else common
+        flags = bind if src in host else common + TU_FLAGS.get(os.path.basename(src), [])
         key = _hash_files([src] + headers, " ".join(flags))
         obj = os.path.join(BUILD, os.path.basename(src) + "." + key + ".o")
         objects.append(obj)

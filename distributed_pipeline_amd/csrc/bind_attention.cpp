@@ -1,6 +1,6 @@
 // Bindings of the attention kernels: training forward / backward (attention.hip,
 // attention128.hip) and the KV-cache decode steps (attn_decode.hip, attn_decode_block.hip,
-// attn_decode_fp8.hip).
+// attn_decode_fp8.hip), with the decode step's Linears beside them (linear_rows.hip).
 #include "bind_util.h"
 
 static std::vector<at::Tensor> attn_fwd(const at::Tensor& qkv, int64_t heads, double p, bool causal,
@@ -267,7 +267,49 @@ static c10::optional<std::vector<at::Tensor>> kv8_quantize(const at::Tensor& x) 
   return std::vector<at::Tensor>{codes, exps};
 }
 
+// A decode step's Linear (csrc/linear_rows.hip): x [M, K] bf16, weight [N, K] bf16 (row-major, a row slice of a
+// larger matrix works), bias [N] bf16 or None, act a code of act.h -> y [M, N] bf16 = act(x W^T + b), or None
+// for a case the kernel does not cover (CPU, dtype, M > 128, K % 64, row layout): the caller's PyTorch path
+// takes it.  `out`: a [M, N] bf16 view to write into (last stride 1, any row stride) instead of a new tensor.
+static c10::optional<at::Tensor> linear_rows(const at::Tensor& x, const at::Tensor& weight,
+                                             c10::optional<at::Tensor> bias, int64_t act,
+                                             c10::optional<at::Tensor> out) {
+  TORCH_CHECK(x.dim() == 2 && weight.dim() == 2, "linear_rows: x [M, K], weight [N, K]");
+  const int64_t M = x.size(0), K = x.size(1), N = weight.size(0);
+  TORCH_CHECK(weight.size(1) == K, "linear_rows: x [M, ", K, "] and weight [N, ", weight.size(1), "] do not agree");
+  TORCH_CHECK(N >= 1, "linear_rows: weight must have N >= 1 rows");
+  TORCH_CHECK(act >= 0 && act <= 3, "linear_rows: act must be 0 (none), 1 (gelu), 2 (tanh) or 3 (silu)");
+  TORCH_CHECK(weight.scalar_type() == x.scalar_type(), "linear_rows: x and weight must have one dtype");
+  if (has(bias)) {
+    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == N, "linear_rows: bias must be [N]");
+    TORCH_CHECK(bias->scalar_type() == x.scalar_type(), "linear_rows: x and bias must have one dtype");
+  }
+  if (has(out))
+    TORCH_CHECK(out->dim() == 2 && out->size(0) == M && out->size(1) == N && out->scalar_type() == x.scalar_type(),
+                "linear_rows: out must be [M, N] in x's dtype");
+  if (!x.is_cuda() || !weight.is_cuda() || weight.device() != x.device()) return c10::nullopt;
+  if (has(bias) && (!bias->is_cuda() || bias->device() != x.device() || !bias->is_contiguous())) return c10::nullopt;
+  if (has(out) && (!out->is_cuda() || out->device() != x.device())) return c10::nullopt;
+  if (x.scalar_type() != at::kBFloat16 || M < 1 || M > 128 || K < 64 || K % 64) return c10::nullopt;
+  auto rows_ok = [&](const at::Tensor& t) {  // last stride 1, 16-byte row starts, rows that do not overlap
+    return t.stride(1) == 1 && (t.size(0) == 1 || (t.stride(0) % 8 == 0 && t.stride(0) >= t.size(1))) &&
+           reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+  };
+  if (!rows_ok(x) || !rows_ok(weight)) return c10::nullopt;
+  if (has(out) && ((N > 1 && out->stride(1) != 1) || (M > 1 && out->stride(0) < N))) return c10::nullopt;
+  const c10::DeviceGuard guard(x.device());
+  at::Tensor y = has(out) ? *out : at::empty({M, N}, x.options());
+  const bool ok = dpa::launch_linear_rows(bf_ptr(x), M > 1 ? x.stride(0) : K, bf_ptr(weight), N > 1 ? weight.stride(0) : K,
+                                          opt_bf_ptr(bias), bf_mut(y), M > 1 ? y.stride(0) : N, (int)M, N, (int)K,
+                                          (int)act, cur_stream());
+  if (!ok) return c10::nullopt;
+  return y;
+}
+
 void dpa::register_attention(pybind11::module& m) {
+  m.def("linear_rows", &linear_rows,
+        "a decode step's Linear: x [M <= 128, K % 64 == 0] bf16 against weight [N, K] bf16 (+ bias [N], act code) -> y [M, N] bf16, each output row a function of its input row alone | None (case not covered)",
+        py::arg("x"), py::arg("weight"), py::arg("bias") = py::none(), py::arg("act") = 0, py::arg("out") = py::none());
   m.def("attn128_supports", &dpa::attn128_supports, "the persistent L = 128 attention covers (L, D, causal)");
   m.def("attn_fwd", &attn_fwd, "fused attention forward (head_dim 64/128) -> (out, lse)", py::arg("qkv"),
         py::arg("heads"), py::arg("p"), py::arg("causal"), py::arg("seed"), py::arg("offset"),

@@ -270,6 +270,17 @@ bool launch_attn_decode_block(const uint16_t* qkv_new, int64_t qkv_sb, int64_t q
                               const int* lens, const int* counts, int B, int T, int H, int Lmax, int D,
                               uint16_t* out, hipStream_t s);
 
+// ---- linear_rows.hip: the Linears of a decode step, 1 .. 128 rows against a whole weight (K-M26) ----
+// y[m][n] = bf16(act(sum_k x[m][k] W[n][k] + bias[n])): x [M][K], W [N][K] and y [M][N] bf16 with rows ldx, ldw
+// and ldy elements apart, bias [N] bf16 or null, act a code of act.h (0 .. 3); fp32 products, sums, bias add
+// and act, one rounding.  The bits of y[m][n] depend on x[m][:], W[n][:], bias[n], act, K and N alone - not on
+// M, the row's place or the other rows.  One launch, no workspace, no atomics.  Rows m >= M and weight rows
+// n >= N are neither loaded nor stored.  false, with no launch: M outside 1 .. 128, N < 1, K no positive
+// multiple of 64, ldx < K, ldw < K, ldy < N, ldx or ldw no multiple of 8, x or W not 16-byte aligned, an
+// unknown act or a null pointer.
+bool launch_linear_rows(const uint16_t* x, int64_t ldx, const uint16_t* W, int64_t ldw, const uint16_t* bias,
+                        uint16_t* y, int64_t ldy, int M, int64_t N, int K, int act, hipStream_t s);
+
 // ---- beam_step.hip: log-softmax + score + top-W of W V candidates (beam search) ----------
 // logits [B][W][V] fp32 or bf16 (element strides stride_b, stride_w >= 0 - 0 repeats a row - and 1),
 // scores fp32 [B][W], finished bytes [B][W] -> the first W candidates of each b in the order

@@ -93,26 +93,58 @@ class GPT2LMModel(nn.Module):
         return KVCache(len(self.h), batch, cfg["num_heads"], max_len, cfg["hidden_size"] // cfg["num_heads"],
                        device, dtype, kv_dtype=kv_dtype)
 
-    def _blocks(self, x, a, attend):
+    def _rows(self, decode_linears, n_rows, ref):
+        """Whether a call of ``n_rows`` rows on ``ref``'s device runs its Linears through
+        ``ops.decode.linear_rows``: asked for, at most 128 rows, bf16 compute on a HIP device."""
+        if decode_linears not in ("tile", "rows"):
+            raise ValueError(f"decode_linears must be 'tile' or 'rows', got {decode_linears!r}")
+        from ..ops.decode import ROWS_MAX_M
+        return (decode_linears == "rows" and n_rows <= ROWS_MAX_M and ref.is_cuda
+                and self.compute_dtype == torch.bfloat16)
+
+    def _lin_rows(self, lin, t):
+        """``lin(t)`` for a ``layers.Linear`` through ``ops.decode.linear_rows`` on the bf16 shadows."""
+        from ..ops.decode import linear_rows
+        dt = self.compute_dtype
+        y = linear_rows(t.reshape(-1, t.shape[-1]), ops.shadow(lin.weight, dt), ops.shadow(lin.bias, dt), act=lin.act)
+        return y.view(*t.shape[:-1], -1)
+
+    def _head(self, a, rows):
+        """The tied head on ``a`` [R, H] -> logits [R, V]."""
+        if rows:
+            from ..ops.decode import linear_rows
+            return linear_rows(a, ops.shadow(self.wte.weight, self.compute_dtype))
+        return ops.linear(a, self.wte.weight)
+
+    def _blocks(self, x, a, attend, rows=False):
         """The block stack of ``hidden_states`` in eval mode with ``attend(i, qkv)`` as layer i's
-        attention over its packed projection -> ln_f of the last residual stream."""
+        attention over its packed projection -> ln_f of the last residual stream.  ``rows``: the four
+        Linears of every block run through ``ops.decode.linear_rows`` (:meth:`_rows` says when)."""
         lns = [blk.ln_1 for blk in self.h] + [self.ln_f]
         for i, blk in enumerate(self.h):
-            h = blk.attn_proj(attend(i, blk.attn.qkv(a)))
+            if rows:
+                h = self._lin_rows(blk.attn_proj, attend(i, self._lin_rows(blk.attn.qkv, a)))
+            else:
+                h = blk.attn_proj(attend(i, blk.attn.qkv(a)))
             x, a = ops.residual_layernorm(h, x, blk.ln_2.weight, blk.ln_2.bias, 0.0, blk.ln_2.eps, False)
-            x, a = ops.residual_layernorm(ops.mlp(a, blk.mlp_fc, blk.mlp_proj), x, lns[i + 1].weight,
-                                          lns[i + 1].bias, 0.0, lns[i + 1].eps, False)
+            if rows:
+                h = self._lin_rows(blk.mlp_proj, self._lin_rows(blk.mlp_fc, a))
+            else:
+                h = ops.mlp(a, blk.mlp_fc, blk.mlp_proj)
+            x, a = ops.residual_layernorm(h, x, lns[i + 1].weight, lns[i + 1].bias, 0.0, lns[i + 1].eps, False)
         return a
 
     @torch.no_grad()
-    def prefill(self, input_ids, lens, cache):
+    def prefill(self, input_ids, lens, cache, decode_linears="tile"):
         """Right-padded prompts ``input_ids`` [B, Lp] of ``1 <= lens[b] <= Lp`` tokens: one causal
         forward (what stands behind a row's prompt never reaches it), each layer's K and V of the
         prompt positions copied into ``cache`` (quantized into an fp8 cache; the prompt's own forward
         attends over the unquantized values), ``cache.lens = lens`` -> the logits [B, V] at each row's
-        last prompt position."""
+        last prompt position.  ``decode_linears="rows"``: the head on those B rows runs through
+        ``ops.decode.linear_rows`` (see :meth:`decode_step`); the prompt's forward is unchanged."""
         dt = self.compute_dtype
         B, Lp = input_ids.shape
+        head_rows = self._rows(decode_linears, B, input_ids)
         if Lp > cache.max_len or B != cache.batch:
             raise ValueError(f"prompts [{B}, {Lp}] do not fit a cache of {cache.batch} rows x {cache.max_len}")
         lens = lens.to(device=input_ids.device, dtype=torch.int32)
@@ -141,21 +173,29 @@ class GPT2LMModel(nn.Module):
         a = self._blocks(x, a, attend)
         cache.lens = lens.clone()
         last = a[torch.arange(B, device=a.device), (lens.long() - 1).clamp(0, Lp - 1)]
-        return ops.linear(last, self.wte.weight)
+        return self._head(last, head_rows)
 
     @torch.no_grad()
-    def decode_step(self, tokens, cache, table=None):
+    def decode_step(self, tokens, cache, table=None, decode_linears="tile"):
         """One token per row at position ``cache.lens[b]`` -> the next-token logits [B, V];
         ``cache.lens`` advances on the device.  A parked row (``lens`` outside 0 .. max_len - 1)
         does no cache work, keeps its ``lens``, and its logits mean nothing.  ``table``: a pair
         ``(src uint8 [B, max_len], beams)`` handed to ``attention_decode`` - the rows are groups
         of ``beams`` slots that read their cached keys through ``src`` (beam search; not over an
-        fp8 cache).  Over an fp8 cache the step is ``ops.decode.attention_decode_fp8``."""
+        fp8 cache).  Over an fp8 cache the step is ``ops.decode.attention_decode_fp8``.
+
+        ``decode_linears``: "tile" (the default) runs the Linears through ``ops.linear``, the B rows
+        padded into the training GEMM's tiles.  "rows" runs qkv, attn_proj, mlp_fc with its GELU,
+        mlp_proj and the tied head through ``ops.decode.linear_rows`` on the bf16 shadows - one launch
+        each, an output row a function of its input row alone - where the call has at most 128 rows and
+        computes in bf16 on a HIP device; anywhere else it is "tile".  The residual adds, the
+        LayerNorms and the attention are the same in both.  The two modes round differently."""
         from ..ops.decode import attention_decode, attention_decode_fp8
         if cache.fp8 and table is not None:
             raise ValueError("an fp8 cache has no indirection-table variant: beam search needs kv_dtype='bf16'")
         dt = self.compute_dtype
         B = tokens.shape[0]
+        rows = self._rows(decode_linears, B, tokens)
         heads = cache.heads
         pos = cache.lens.long().clamp(0, self.cfg["max_position_embeddings"] - 1)
         # the B rows stand where hidden_states has the L positions of one sequence, so the
@@ -172,15 +212,15 @@ class GPT2LMModel(nn.Module):
                                             cache.lens, heads).view(1, B, -1)
             return attention_decode(qkv.view(B, -1), cache.k[i], cache.v[i], cache.lens, heads, **kw).view(1, B, -1)
 
-        a = self._blocks(x, a, attend)
+        a = self._blocks(x, a, attend, rows)
         cache.lens += ((cache.lens >= 0) & (cache.lens < cache.max_len)).to(cache.lens.dtype)
-        return ops.linear(a.view(B, -1), self.wte.weight)
+        return self._head(a.view(B, -1), rows)
 
     @torch.no_grad()
     def generate(self, input_ids, lens, max_new_tokens, *, temperature=1.0, top_k=0, top_p=0.0, eos_id=None,
                  generator=None, cache=None, check_every=16, noise_seed=None, row_base=0, repetition_penalty=1.0,
                  presence_penalty=0.0, frequency_penalty=0.0, no_repeat_ngram=0, min_new_tokens=0,
-                 penalize_prompt=True, return_logprobs=False, kv_dtype=None):
+                 penalize_prompt=True, return_logprobs=False, kv_dtype=None, decode_linears="tile"):
         """Continue right-padded prompts -> (tokens [B, max_new_tokens], new_lens [B]).
 
         ``temperature == 0`` is greedy (ties to the lowest id); otherwise ``logits / temperature``,
@@ -194,7 +234,8 @@ class GPT2LMModel(nn.Module):
         ``cache``: one from :meth:`init_cache` to use (default: a new one of just the size needed).
         ``kv_dtype``: "bf16" or "fp8" - the one-byte cache, half the bytes per cached token - for
         the new cache (default "bf16"); given together with a ``cache`` of the other kind it is an
-        error.
+        error.  ``decode_linears``: "tile" or "rows", handed to :meth:`prefill` and every
+        :meth:`decode_step`.
         The loop runs on the device; the host looks at it once every ``check_every`` steps (0:
         never), to stop early when every row has finished.
 
@@ -220,6 +261,8 @@ class GPT2LMModel(nn.Module):
         dev = input_ids.device
         if kv_dtype not in (None, "bf16", "fp8"):
             raise ValueError(f"kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}")
+        self._rows(decode_linears, B, input_ids)  # an unknown value raises here
+        dl = {} if decode_linears == "tile" else {"decode_linears": decode_linears}
         if cache is None:
             cache = self.init_cache(B, min(Lp + max_new_tokens, self.cfg["max_position_embeddings"]), dev,
                                     **({"kv_dtype": "fp8"} if kv_dtype == "fp8" else {}))
@@ -237,7 +280,7 @@ class GPT2LMModel(nn.Module):
             hist[:, :Lp] = input_ids
             n = lens.to(device=dev, dtype=torch.int32).clone()
             start = None if penalize_prompt else n.clone()
-        logits = self.prefill(input_ids, lens, cache)
+        logits = self.prefill(input_ids, lens, cache, **dl)
         for t in range(max_new_tokens):
             if t < min_new:
                 logits[:, fill] = float("-inf")  # every live row has produced t tokens
@@ -264,7 +307,7 @@ class GPT2LMModel(nn.Module):
             cache.lens.masked_fill_(done, -1)
             if check_every and (t + 1) % check_every == 0 and bool(done.all()):
                 break
-            logits = self.decode_step(tok, cache)
+            logits = self.decode_step(tok, cache, **dl)
         cache.lens.masked_fill_(done, -1)
         return (out, new_lens, logprobs) if return_logprobs else (out, new_lens)
 
@@ -349,18 +392,19 @@ class GPT2LMModel(nn.Module):
         return res
 
     @torch.no_grad()
-    def decode_block(self, tokens, cache, counts=None):
+    def decode_block(self, tokens, cache, counts=None, decode_linears="tile"):
         """T tokens per row, token j of row b at position ``cache.lens[b] + j`` -> logits [B, T, V],
         the logits at j saying what follows token j.  ``counts`` (int [B], default T): how many of a
         row's tokens are real - ``ops.decode.attention_decode_block`` has the exact rule; the logits of
         the others mean nothing and their keys are not stored.  ``cache.lens`` is NOT advanced: the
         caller commits as many positions as it accepted, and what was stored beyond them is
-        overwritten or never read."""
+        overwritten or never read.  ``decode_linears``: as in :meth:`decode_step`, for the B T rows."""
         from ..ops.decode import attention_decode_block
         if cache.fp8:
             raise ValueError("decode_block has no fp8 variant: lookahead decoding needs kv_dtype='bf16'")
         dt = self.compute_dtype
         B, T = tokens.shape
+        rows = self._rows(decode_linears, B * T, tokens)
         heads = cache.heads
         pos = cache.lens.long().view(B, 1) + torch.arange(T, device=tokens.device).view(1, T)
         pos = pos.clamp(0, self.cfg["max_position_embeddings"] - 1).view(-1)
@@ -375,14 +419,14 @@ class GPT2LMModel(nn.Module):
             return attention_decode_block(qkv.view(B, T, -1), cache.k[i], cache.v[i], cache.lens, heads,
                                           counts=counts).view(1, B * T, -1)
 
-        a = self._blocks(x, a, attend)
-        return ops.linear(a.view(B * T, -1), self.wte.weight).view(B, T, -1)
+        a = self._blocks(x, a, attend, rows)
+        return self._head(a.view(B * T, -1), rows).view(B, T, -1)
 
     @torch.no_grad()
     def generate_lookahead(self, input_ids, lens, max_new_tokens, *, lookahead, ngram=2, eos_id=None, cache=None,
                            check_every=4, draft=None, return_stats=False, repetition_penalty=1.0,
                            presence_penalty=0.0, frequency_penalty=0.0, no_repeat_ngram=0, min_new_tokens=0,
-                           penalize_prompt=True):
+                           penalize_prompt=True, decode_linears="tile"):
         """Greedy continuation by lookahead decoding -> (tokens [B, max_new_tokens], new_lens [B]),
         with the meanings of :meth:`generate`: its ``temperature=0`` result wherever every arg-max on
         the way is the same in both, in fewer model calls.
@@ -403,6 +447,7 @@ class GPT2LMModel(nn.Module):
         max_draft) -> (draft [B, max_draft], k [B])`` to use instead - ``history[b, :n[b]]`` is the
         row's prompt and output so far.  ``return_stats`` adds a dict: ``model_calls`` (iterations with
         a live row), ``proposed`` and ``accepted`` guesses, read back once at the end.
+        ``decode_linears``: "tile" or "rows", handed to :meth:`prefill` and every :meth:`decode_block`.
 
         The logit processors of :meth:`generate` are not available here: the guesses continue
         repeated n-grams, which is what those penalties forbid, and the queries of a block would
@@ -421,6 +466,8 @@ class GPT2LMModel(nn.Module):
         draft = lookup_draft if draft is None else draft
         B, Lp = input_ids.shape
         dev = input_ids.device
+        self._rows(decode_linears, B, input_ids)  # an unknown value raises here
+        dl = {} if decode_linears == "tile" else {"decode_linears": decode_linears}
         if cache is None:
             cache = self.init_cache(B, min(Lp + N, self.cfg["max_position_embeddings"]), dev)
         elif cache.fp8:
@@ -436,7 +483,7 @@ class GPT2LMModel(nn.Module):
         new_lens = torch.zeros(B, dtype=torch.long, device=dev)
         done = torch.zeros(B, dtype=torch.bool, device=dev)
         stats = torch.zeros(3, dtype=torch.long, device=dev)  # model calls, proposed, accepted
-        logits = self.prefill(input_ids, lens, cache)
+        logits = self.prefill(input_ids, lens, cache, **dl)
         if N == 0:
             res = (out[:, :0], new_lens)
             return res + ({"model_calls": 0, "proposed": 0, "accepted": 0},) if return_stats else res
@@ -459,7 +506,7 @@ class GPT2LMModel(nn.Module):
             counts = torch.minimum(torch.minimum(1 + k.long(), max_len - pos.long()), N - new_lens)
             counts = torch.where(idle, 0, counts).clamp(min=0)
             block = torch.cat([last.view(B, 1), guess], 1)
-            logits = self.decode_block(block, cache, counts)
+            logits = self.decode_block(block, cache, counts, **dl)
             picks = greedy(logits.view(B * T, -1)).view(B, T)
             # a: the guesses accepted - the longest prefix with block[j + 1] == picks[j], j + 1 < counts
             match = (block[:, 1:] == picks[:, :-1]) & (cols[:, 1:] < counts.view(B, 1))
@@ -491,7 +538,7 @@ class GPT2LMModel(nn.Module):
     @torch.no_grad()
     def beam_search(self, input_ids, lens, max_new_tokens, *, num_beams, eos_id=None, length_penalty=0.0,
                     cache=None, check_every=16, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
-                    no_repeat_ngram=0, min_new_tokens=0, penalize_prompt=True):
+                    no_repeat_ngram=0, min_new_tokens=0, penalize_prompt=True, decode_linears="tile"):
         """Continue right-padded prompts with beam search -> (tokens [B, W, max_new_tokens], new_lens
         [B, W], scores fp32 [B, W]), ``W = num_beams``, the beams of a prompt best first.
 
@@ -519,7 +566,10 @@ class GPT2LMModel(nn.Module):
         common position, and ``ops.decode.penalize_logits_`` runs on every step's logits before
         ``beam_step`` (finished and non-existent slots are passed as parked rows).  The first step's
         logits are one row per prompt repeated for every beam, so they are penalised once, before
-        they are expanded.  The scores are sums of the log-softmax of the processed logits."""
+        they are expanded.  The scores are sums of the log-softmax of the processed logits.
+
+        ``decode_linears``: "tile" or "rows", handed to :meth:`prefill` and every :meth:`decode_step`
+        (``B W`` rows)."""
         from ..ops.decode import beam_step, penalize_logits_
         penalties, min_new = _logit_processors(repetition_penalty, presence_penalty, frequency_penalty,
                                                no_repeat_ngram, min_new_tokens, eos_id)
@@ -529,6 +579,8 @@ class GPT2LMModel(nn.Module):
         B, Lp = input_ids.shape
         dev = input_ids.device
         T = int(max_new_tokens)
+        self._rows(decode_linears, B * W, input_ids)  # an unknown value raises here
+        dl = {} if decode_linears == "tile" else {"decode_linears": decode_linears}
         if cache is None:
             cache = self.init_cache(B * W, min(Lp + T, self.cfg["max_position_embeddings"]), dev)
         elif cache.fp8:
@@ -541,7 +593,7 @@ class GPT2LMModel(nn.Module):
         eos = -1 if eos_id is None else int(eos_id)
         ninf = float("-inf")
 
-        logits = self.prefill(input_ids, lens, cache.slot_view(W, 0))  # the prompts, once, into slot 0
+        logits = self.prefill(input_ids, lens, cache.slot_view(W, 0), **dl)  # the prompts, once, into slot 0
         if min_new > 0:
             logits[:, fill] = ninf
         if penalties is not None:
@@ -588,7 +640,7 @@ class GPT2LMModel(nn.Module):
             cur ^= 1
             cache.table = nxt
             cache.lens.copy_(torch.where(active, glen.view(B, 1), -1).view(-1))
-            logits = self.decode_step(token.view(-1), cache, table=(nxt.view(B * W, Lmax), W)).view(B, W, -1)
+            logits = self.decode_step(token.view(-1), cache, table=(nxt.view(B * W, Lmax), W), **dl).view(B, W, -1)
             glen = glen + (glen < Lmax).to(glen.dtype)
             if t + 1 < min_new:
                 logits[:, :, fill] = ninf  # every live beam has produced t + 1 tokens

@@ -2,8 +2,9 @@
 The per-token ops of GPT-2 generation: single-query attention over a K/V cache (directly, or through
 the indirection table of a beam search), the same for a block of new tokens with the guesses that
 fill it (lookahead decoding), one beam-search step, the choice of the next token, the logit
-processors in front of it (repetition, presence and frequency penalty, no-repeat-n-gram ban), and
-the statistics of a logits row against a given token (teacher-forced scoring).
+processors in front of it (repetition, presence and frequency penalty, no-repeat-n-gram ban), the
+statistics of a logits row against a given token (teacher-forced scoring), and the Linears of a
+decode step, whose few rows stand against whole weight matrices.
 
 Attention of one decode step
 ----------------------------
@@ -247,11 +248,36 @@ one 4-byte store per output and row, no workspace, no atomics, nothing read back
 for bit.  Anything else (CPU, other dtypes, a larger V): :func:`token_stats_ref`, the same definition
 in fp32 PyTorch over chunks of rows.  The two paths may differ by fp32 rounding in the two floats;
 the two integers are exact on both.
+
+The Linears of a decode step: ``linear_rows``
+---------------------------------------------
+``linear_rows(x [M, K], weight [N, K], bias [N] | None = None, *, act="none") -> y [M, N]`` in ``x``'s dtype:
+
+* ``y[m, n] = round_to_dtype(act(sum_k x[m, k] * W[n, k] + b[n]))``: products and the sum in fp32, the
+  bias added in fp32, ``act`` ("none", "gelu", "tanh", "silu": the codes and functions of csrc/act.h)
+  applied to the fp32 value, one rounding to the output dtype.
+* ``weight`` is the row-major ``[N, K]`` matrix every ``layers.Linear`` and the tied ``wte`` hold: no
+  transposed copy.  Inference only: no autograd.  ``M == 0`` returns an empty tensor.
+
+The row contract (the kernel path).  The bits of ``y[m, n]`` are a function of ``x[m, :]``, ``W[n, :]``,
+``b[n]``, ``act``, K and N.  They do not depend on M, on where the row stands in the call, on what the
+other rows hold, or on the launch geometry: one MFMA shape and one k order serve every M, K is split
+among the four waves of a workgroup by (K) alone and never across workgroups, and the partial sums are
+added in wave order by one writer per element, without atomics.  A row of a 12-row call equals the same
+row of a 4-row call bit for bit, and two calls agree bit for bit.
+
+bf16 ``x`` on a HIP device with last stride 1 and 16-byte aligned rows, ``1 <= M <= 128``, K a multiple
+of 64 and any ``N >= 1``; ``weight`` bf16 with last stride 1 and 16-byte aligned rows (a row stride above
+K, such as a row slice of a larger matrix, is served); ``bias`` bf16 or absent: one launch of
+csrc/linear_rows.hip.  Anything else (CPU, fp32, a larger M, another K): :func:`linear_rows_ref`, the
+definition in fp32 PyTorch (its GELU is the exact one; the kernel's is ``gelu_f``, below bf16 resolution
+of it).
 """
 import math
 import struct
 
 import torch
+import torch.nn.functional as F
 
 from ._ext import get_ext
 
@@ -926,3 +952,45 @@ def token_stats(logits, targets):
             if out is not None:
                 return tuple(out)
     return token_stats_ref(logits, targets)
+
+
+# ---- linear_rows --------------------------------------------------------------------------------
+
+ROWS_MAX_M = 128  # the most rows csrc/linear_rows.hip takes
+_ROWS_ACTS = {"none": 0, "gelu": 1, "tanh": 2, "silu": 3}  # csrc/act.h
+
+
+def _check_linear_rows(x, weight, bias, act):
+    if act not in _ROWS_ACTS:
+        raise ValueError(f"act must be one of {sorted(_ROWS_ACTS)}, got {act!r}")
+    if x.dim() != 2 or weight.dim() != 2 or weight.shape[1] != x.shape[1] or weight.shape[0] < 1:
+        raise ValueError(f"x must be [M, K] and weight [N >= 1, K], got {tuple(x.shape)}, {tuple(weight.shape)}")
+    if bias is not None and tuple(bias.shape) != (weight.shape[0],):
+        raise ValueError(f"bias must be [{weight.shape[0]}], got {tuple(bias.shape)}")
+
+
+def linear_rows_ref(x, weight, bias=None, *, act="none"):
+    """The definition in fp32 PyTorch (any device, any float dtype) -> y [M, N] in ``x``'s dtype."""
+    _check_linear_rows(x, weight, bias, act)
+    z = F.linear(x.detach().float(), weight.detach().float(), None if bias is None else bias.detach().float())
+    z = {"none": lambda t: t, "gelu": F.gelu, "tanh": torch.tanh, "silu": F.silu}[act](z)
+    return z.to(x.dtype)
+
+
+@torch.no_grad()
+def linear_rows(x, weight, bias=None, *, act="none"):
+    """-> y [M, N] = act(x W^T + b) in ``x``'s dtype, each output row a function of its input row alone:
+    the module docstring has the definition and the row contract."""
+    _check_linear_rows(x, weight, bias, act)
+    if x.shape[0] == 0:
+        return x.new_empty(0, weight.shape[0])
+    if x.is_cuda:
+        ext = get_ext()  # raises on a GPU without the built extension: no quiet fall-back
+        if ext is not None and x.dtype == torch.bfloat16 and weight.dtype == x.dtype and (
+                bias is None or bias.dtype == x.dtype):
+            if x.stride(-1) != 1 or x.stride(0) % 8 or x.data_ptr() % 16:
+                x = x.contiguous()
+            out = ext.linear_rows(x, weight, None if bias is None else bias.contiguous(), _ROWS_ACTS[act])
+            if out is not None:
+                return out
+    return linear_rows_ref(x, weight, bias, act=act)

@@ -41,6 +41,12 @@ exponent per cached row (``ops.decode`` has the format): half the cache memory a
 decode step reads.  Its continuations are those of a slightly different model, not bf16's bit for bit.
 It combines with sampling, ``--noise philox``, the penalties and ``--logprobs`` and excludes
 ``--num_beams > 1`` and ``--lookahead``.  The default is ``bf16``.
+
+``--decode_linears rows`` runs the Linears of every decode step - qkv, attn_proj, mlp_fc, mlp_proj and the
+tied head - through ``ops.decode.linear_rows``, a kernel that streams each weight once for the step's few
+rows, instead of padding the rows into the training GEMM's tiles (``tile``, the default).  It applies where
+a step has at most 128 rows (``--batch_size`` times ``--num_beams`` or ``--lookahead``) in bf16 on a GPU and
+combines with every other flag.  The two modes round differently, so continuations can differ.
 """
 import json
 import os
@@ -91,6 +97,7 @@ def main(namespace):
     gen.manual_seed(args.seed)
     eos = None if args.eos_id < 0 else args.eos_id
     Lp, Ln = args.prompt_len, args.max_new_tokens
+    dl = {"decode_linears": args.decode_linears} if args.decode_linears != "tile" else {}
     n = 0
     look = {"model_calls": 0, "tokens": 0, "proposed": 0, "accepted": 0}
     with open(out_path, "w") as fout:
@@ -102,13 +109,13 @@ def main(namespace):
             if args.num_beams > 1:
                 beams, beam_lens, beam_scores = model.beam_search(
                     ids[:, :Lp].contiguous(), lens, Ln, num_beams=args.num_beams, eos_id=eos,
-                    length_penalty=args.length_penalty, **args.logit_processors())
+                    length_penalty=args.length_penalty, **args.logit_processors(), **dl)
                 beams, beam_lens, beam_scores = beams.cpu(), beam_lens.cpu(), beam_scores.cpu()
                 toks, new_lens = beams[:, 0], beam_lens[:, 0]
             elif args.lookahead:
                 toks, new_lens, stats = model.generate_lookahead(
                     ids[:, :Lp].contiguous(), lens, Ln, lookahead=args.lookahead, ngram=args.lookup_ngram,
-                    eos_id=eos, return_stats=True)
+                    eos_id=eos, return_stats=True, **dl)
                 for key, val in stats.items():
                     look[key] += val
                 look["tokens"] += int(new_lens.sum())
@@ -117,7 +124,7 @@ def main(namespace):
                                      top_k=args.top_k, top_p=args.top_p, eos_id=eos, generator=gen,
                                      noise_seed=args.seed if args.noise == "philox" else None, row_base=n,
                                      **args.logit_processors(), **({"return_logprobs": True} if args.logprobs else {}),
-                                     **({"kv_dtype": args.kv_dtype} if args.kv_dtype != "bf16" else {}))
+                                     **({"kv_dtype": args.kv_dtype} if args.kv_dtype != "bf16" else {}), **dl)
                 toks, new_lens = res[:2]
                 if args.logprobs:
                     logprobs = res[2].cpu()
