@@ -87,6 +87,11 @@ class ContinueSettings(S):
                     "per Linear and the tied head included, where a step has at most 128 rows; an output row is "
                     "then a function of its input row alone. The two round differently, so continuations can "
                     "differ.")
+    prefill_chunk: int \
+        = _(0, "Run the prompts through the cache-extending attention kernel (ops.decode.attention_extend) in "
+               "pieces of this many tokens instead of one causal forward over the padded prompt matrix; 0 = off. "
+               "The two round differently, so continuations can differ. Excludes --kv_dtype fp8, --num_beams > 1 "
+               "and --lookahead.")
     out_path: str \
         = _("", "Output .jsonl file (default: generated_<checkpoint>_seed<seed>.jsonl next to the checkpoint).")
     precision: Choice("bf16", "fp32") \
@@ -138,6 +143,11 @@ class GenerateSettings(
         if self.kv_dtype == "fp8" and (self.num_beams > 1 or self.lookahead > 0):
             raise ValueError("--kv_dtype fp8 is served by generate's own loop: the table (--num_beams > 1) and "
                              "block (--lookahead) decode kernels have no fp8 variant")
+        if self.prefill_chunk < 0:
+            raise ValueError(f"--prefill_chunk must be >= 0, got {self.prefill_chunk}")
+        if self.prefill_chunk > 0 and (self.kv_dtype == "fp8" or self.num_beams > 1 or self.lookahead > 0):
+            raise ValueError("--prefill_chunk is served by generate's own loop over a bf16 cache: it excludes "
+                             "--kv_dtype fp8, --num_beams > 1 and --lookahead")
         if not 0.0 <= self.top_p <= 1.0:
             raise ValueError(f"--top_p must be in [0, 1], got {self.top_p}")
         if self.temperature < 0:

@@ -1,6 +1,6 @@
 // Bindings of the attention kernels: training forward / backward (attention.hip,
 // attention128.hip) and the KV-cache decode steps (attn_decode.hip, attn_decode_block.hip,
-// attn_decode_fp8.hip), with the decode step's Linears beside them (linear_rows.hip).
+// attn_decode_fp8.hip, attn_extend.hip), with the decode step's Linears beside them (linear_rows.hip).
 #include "bind_util.h"
 
 static std::vector<at::Tensor> attn_fwd(const at::Tensor& qkv, int64_t heads, double p, bool causal,
@@ -154,9 +154,12 @@ static c10::optional<at::Tensor> attn_decode_beam(const at::Tensor& qkv_new, at:
 // A block of T new tokens per row (csrc/attn_decode_block.hip): qkv_new [B, T, 3 H D] bf16, counts
 // int32 [B] or None (= T) -> out [B, T, H D] bf16: T successive attn_decode calls in one pass over the
 // caches (launchers.h has the definition), or None for a case the kernel does not cover.
-static c10::optional<at::Tensor> attn_decode_block(const at::Tensor& qkv_new, at::Tensor& k_cache, at::Tensor& v_cache,
-                                                   const at::Tensor& lens, int64_t n_heads,
-                                                   c10::optional<at::Tensor> counts) {
+//
+// attn_extend (csrc/attn_extend.hip) has the same arguments, rule and checks for a run of T <= 128 tokens on
+// the MFMA; a longer run is a case it does not cover.
+static c10::optional<at::Tensor> attn_block_any(const at::Tensor& qkv_new, at::Tensor& k_cache, at::Tensor& v_cache,
+                                                const at::Tensor& lens, int64_t n_heads,
+                                                c10::optional<at::Tensor> counts, bool extend) {
   TORCH_CHECK(qkv_new.dim() == 3 && k_cache.dim() == 4 && v_cache.dim() == 4 && lens.dim() == 1 && n_heads > 0,
               "attn_decode_block: qkv_new [B, T, 3 H D], caches [B, H, Lmax, D], lens [B]");
   const int64_t B = k_cache.size(0), H = k_cache.size(1), Lmax = k_cache.size(2), D = k_cache.size(3);
@@ -164,7 +167,7 @@ static c10::optional<at::Tensor> attn_decode_block(const at::Tensor& qkv_new, at
   TORCH_CHECK(H == n_heads && v_cache.sizes() == k_cache.sizes() && qkv_new.size(0) == B &&
                   qkv_new.size(2) == 3 * H * D && lens.size(0) == B,
               "attn_decode_block: shapes of qkv_new, the caches, lens and n_heads do not agree");
-  TORCH_CHECK(T >= 1 && T <= 8, "attn_decode_block: T must be in 1 .. 8, got ", T);
+  TORCH_CHECK(T >= 1 && (extend || T <= 8), "attn_decode_block: T must be in 1 .. 8, got ", T);
   TORCH_CHECK(lens.scalar_type() == at::kInt, "attn_decode_block: lens must be int32");
   const bool has_counts = counts.has_value() && counts->defined();
   if (has_counts)
@@ -178,6 +181,7 @@ static c10::optional<at::Tensor> attn_decode_block(const at::Tensor& qkv_new, at
       v_cache.scalar_type() != at::kBFloat16)
     return c10::nullopt;
   if ((D != 64 && D != 128) || B == 0 || Lmax == 0 || Lmax > 0x7fffffffLL || B * H > 0x7fffffffLL) return c10::nullopt;
+  if (extend && T > 128) return c10::nullopt;
   auto rows_ok = [&](const at::Tensor& c) {  // packed rows of D; 16-byte row starts
     return c.stride(3) == 1 && c.stride(2) == D && c.stride(0) % 8 == 0 && c.stride(1) % 8 == 0 &&
            reinterpret_cast<uintptr_t>(c.data_ptr()) % 16 == 0;
@@ -188,13 +192,25 @@ static c10::optional<at::Tensor> attn_decode_block(const at::Tensor& qkv_new, at
     return c10::nullopt;
   const c10::DeviceGuard guard(qkv_new.device());
   at::Tensor out = at::empty({B, T, H * D}, qkv_new.options());
-  const bool ok = dpa::launch_attn_decode_block(
+  const bool ok = (extend ? dpa::launch_attn_extend : dpa::launch_attn_decode_block)(
       bf_ptr(qkv_new), qkv_new.stride(0), qkv_new.stride(1), bf_mut(k_cache), bf_mut(v_cache), k_cache.stride(0),
       k_cache.stride(1), v_cache.stride(0), v_cache.stride(1), lens.data_ptr<int>(),
       has_counts ? counts->data_ptr<int>() : nullptr, (int)B, (int)T, (int)H, (int)Lmax, (int)D, bf_mut(out),
       cur_stream());
   if (!ok) return c10::nullopt;
   return out;
+}
+
+static c10::optional<at::Tensor> attn_decode_block(const at::Tensor& qkv_new, at::Tensor& k_cache, at::Tensor& v_cache,
+                                                   const at::Tensor& lens, int64_t n_heads,
+                                                   c10::optional<at::Tensor> counts) {
+  return attn_block_any(qkv_new, k_cache, v_cache, lens, n_heads, counts, false);
+}
+
+static c10::optional<at::Tensor> attn_extend(const at::Tensor& qkv_new, at::Tensor& k_cache, at::Tensor& v_cache,
+                                             const at::Tensor& lens, int64_t n_heads,
+                                             c10::optional<at::Tensor> counts) {
+  return attn_block_any(qkv_new, k_cache, v_cache, lens, n_heads, counts, true);
 }
 
 // The decode step over a one-byte cache (csrc/attn_decode_fp8.hip): qkv_new [B, 3 H D] bf16, k8 / v8 uint8
@@ -331,6 +347,10 @@ void dpa::register_attention(pybind11::module& m) {
         py::arg("src"), py::arg("beams"));
   m.def("attn_decode_block", &attn_decode_block,
         "KV-cache append + attention of a block of T <= 8 new tokens per row, as T successive attn_decode calls in one pass over the caches -> out [B, T, H D] bf16 | None (case not covered)",
+        py::arg("qkv_new"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"), py::arg("n_heads"),
+        py::arg("counts") = py::none());
+  m.def("attn_extend", &attn_extend,
+        "KV-cache append + attention of a run of T <= 128 new tokens per row on the MFMA (attn_decode_block's rule) -> out [B, T, H D] bf16 | None (case not covered)",
         py::arg("qkv_new"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"), py::arg("n_heads"),
         py::arg("counts") = py::none());
   m.def("attn_decode_fp8", &attn_decode_fp8,

@@ -270,6 +270,18 @@ bool launch_attn_decode_block(const uint16_t* qkv_new, int64_t qkv_sb, int64_t q
                               const int* lens, const int* counts, int B, int T, int H, int Lmax, int D,
                               uint16_t* out, hipStream_t s);
 
+// ---- attn_extend.hip: a run of up to 128 new tokens per row against the cache, on the MFMA (K-M27) ----
+// launch_attn_decode_block's arguments and rule for 1 <= T <= 128: tokens j < c_b are stored at cache
+// rows lens[b] + j (the bits of qkv_new) and attend over the keys 0 .. lens[b] + j; queries j >= c_b store
+// nothing and return zeros; cache rows at or beyond lens[b] + c_b are neither read nor written; lens and
+// counts are not modified.  The weights are rounded to bf16 before they meet V, so the results are the
+// block kernel's to bf16 accuracy, not bit for bit; two calls agree bit for bit.  One launch of
+// B H ceil(T / 32) workgroups, no workspace, no atomics.  false, with no launch: as
+// launch_attn_decode, or T outside 1 .. 128, or qkv_st no multiple of 8.
+bool launch_attn_extend(const uint16_t* qkv_new, int64_t qkv_sb, int64_t qkv_st, uint16_t* k_cache,
+                        uint16_t* v_cache, int64_t k_sb, int64_t k_sh, int64_t v_sb, int64_t v_sh, const int* lens,
+                        const int* counts, int B, int T, int H, int Lmax, int D, uint16_t* out, hipStream_t s);
+
 // ---- linear_rows.hip: the Linears of a decode step, 1 .. 128 rows against a whole weight (K-M26) ----
 // y[m][n] = bf16(act(sum_k x[m][k] W[n][k] + bias[n])): x [M][K], W [N][K] and y [M][N] bf16 with rows ldx, ldw
 // and ldy elements apart, bias [N] bf16 or null, act a code of act.h (0 .. 3); fp32 products, sums, bias add

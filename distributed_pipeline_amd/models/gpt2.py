@@ -135,19 +135,41 @@ class GPT2LMModel(nn.Module):
         return a
 
     @torch.no_grad()
-    def prefill(self, input_ids, lens, cache, decode_linears="tile"):
+    def prefill(self, input_ids, lens, cache, decode_linears="tile", chunk=0):
         """Right-padded prompts ``input_ids`` [B, Lp] of ``1 <= lens[b] <= Lp`` tokens: one causal
         forward (what stands behind a row's prompt never reaches it), each layer's K and V of the
         prompt positions copied into ``cache`` (quantized into an fp8 cache; the prompt's own forward
         attends over the unquantized values), ``cache.lens = lens`` -> the logits [B, V] at each row's
         last prompt position.  ``decode_linears="rows"``: the head on those B rows runs through
-        ``ops.decode.linear_rows`` (see :meth:`decode_step`); the prompt's forward is unchanged."""
+        ``ops.decode.linear_rows`` (see :meth:`decode_step`); the prompt's forward is unchanged.
+
+        ``chunk = C >= 1``: the prompt goes through :meth:`extend` in pieces of C columns instead,
+        starting from an empty cache - piece ``p0`` with ``counts = clamp(lens - p0, 0, C)``, so nothing is
+        padded to the longest prompt's next multiple of 64 and K and V reach the cache inside the
+        attention kernel.  Each row's hidden state at position ``lens - 1`` is taken from the piece that
+        holds it and the head runs once on those B rows.  Not over an fp8 cache.  0: the single forward."""
         dt = self.compute_dtype
         B, Lp = input_ids.shape
         head_rows = self._rows(decode_linears, B, input_ids)
         if Lp > cache.max_len or B != cache.batch:
             raise ValueError(f"prompts [{B}, {Lp}] do not fit a cache of {cache.batch} rows x {cache.max_len}")
         lens = lens.to(device=input_ids.device, dtype=torch.int32)
+        C = int(chunk)
+        if C < 0:
+            raise ValueError(f"chunk must be >= 0, got {chunk}")
+        if C:
+            if cache.fp8:
+                raise ValueError("a chunked prefill has no fp8 variant: it needs kv_dtype='bf16'")
+            cache.lens = torch.zeros_like(lens)
+            rows = torch.arange(B, device=input_ids.device)
+            last = None
+            for p0 in range(0, Lp, C):
+                ids = input_ids[:, p0:p0 + C]
+                hid = self.extend(ids, cache, (lens - p0).clamp(0, ids.shape[1]), decode_linears)
+                at = lens.long() - 1 - p0  # where the row's last prompt token stands in this piece
+                mine = hid[rows, at.clamp(0, ids.shape[1] - 1)]
+                last = mine if last is None else torch.where((at >= 0).view(B, 1), mine, last)
+            return self._head(last, head_rows)
         L = Lp
         if input_ids.is_cuda and dt == torch.bfloat16 and Lp % 64:
             # ops.attention's kernels take L % 64 == 0: pad on the right, which causality hides
@@ -174,6 +196,47 @@ class GPT2LMModel(nn.Module):
         cache.lens = lens.clone()
         last = a[torch.arange(B, device=a.device), (lens.long() - 1).clamp(0, Lp - 1)]
         return self._head(last, head_rows)
+
+    @torch.no_grad()
+    def extend(self, tokens, cache, counts=None, decode_linears="tile"):
+        """Append T tokens per row to a cache that may already hold something, token j of row b at
+        position ``cache.lens[b] + j`` -> the hidden states [B, T, H] after ``ln_f``; the head is the
+        caller's (a chunked prefill needs one row of them).  ``counts`` (int [B], default T): how many
+        of a row's tokens are real - ``c_b`` of ``ops.decode.attention_extend``; the hidden states of
+        the others mean nothing and their keys are not stored.  ``cache.lens`` advances by ``c_b`` on
+        the device; a parked row does no cache work and keeps its ``lens``.  Runs longer than the
+        kernel's 128 tokens go through the stack in pieces of 128.  ``decode_linears``: as in
+        :meth:`decode_step`, for the rows of a piece.  Not over an fp8 cache."""
+        from ..ops.decode import EXTEND_MAX, attention_extend
+        if cache.fp8:
+            raise ValueError("extend has no fp8 variant: it needs kv_dtype='bf16'")
+        dt = self.compute_dtype
+        B, T = tokens.shape
+        if T < 1 or B != cache.batch:
+            raise ValueError(f"tokens [{B}, {T}] do not fit a cache of {cache.batch} rows")
+        heads = cache.heads
+        lens = cache.lens
+        counts = torch.full_like(lens, T) if counts is None else counts.to(device=lens.device, dtype=torch.int32)
+        ln0 = self.h[0].ln_1
+        outs = []
+        for t0 in range(0, T, EXTEND_MAX):
+            Tc = min(EXTEND_MAX, T - t0)
+            rows = self._rows(decode_linears, B * Tc, tokens)
+            cnt = (counts - t0).clamp(0, Tc)
+            pos = lens.long().view(B, 1) + torch.arange(Tc, device=tokens.device).view(1, Tc)
+            pos = pos.clamp(0, self.cfg["max_position_embeddings"] - 1).view(-1)
+            # the B Tc tokens stand where decode_step has its B rows: the same kernels around the attention
+            x, a = ops.residual_layernorm(self.wte(tokens[:, t0:t0 + Tc].reshape(1, B * Tc), dt), None, ln0.weight,
+                                          ln0.bias, 0.0, ln0.eps, False, pos=self.wpe(pos, dt))
+
+            def attend(i, qkv):
+                return attention_extend(qkv.view(B, Tc, -1), cache.k[i], cache.v[i], lens, heads,
+                                        counts=cnt).view(1, B * Tc, -1)
+
+            outs.append(self._blocks(x, a, attend, rows).view(B, Tc, -1))
+            active = (lens >= 0) & (lens < cache.max_len)
+            lens += torch.where(active, torch.minimum(cnt, cache.max_len - lens), 0).to(lens.dtype)
+        return outs[0] if len(outs) == 1 else torch.cat(outs, 1)
 
     @torch.no_grad()
     def decode_step(self, tokens, cache, table=None, decode_linears="tile"):
@@ -220,7 +283,8 @@ class GPT2LMModel(nn.Module):
     def generate(self, input_ids, lens, max_new_tokens, *, temperature=1.0, top_k=0, top_p=0.0, eos_id=None,
                  generator=None, cache=None, check_every=16, noise_seed=None, row_base=0, repetition_penalty=1.0,
                  presence_penalty=0.0, frequency_penalty=0.0, no_repeat_ngram=0, min_new_tokens=0,
-                 penalize_prompt=True, return_logprobs=False, kv_dtype=None, decode_linears="tile"):
+                 penalize_prompt=True, return_logprobs=False, kv_dtype=None, decode_linears="tile",
+                 prefill_chunk=0):
         """Continue right-padded prompts -> (tokens [B, max_new_tokens], new_lens [B]).
 
         ``temperature == 0`` is greedy (ties to the lowest id); otherwise ``logits / temperature``,
@@ -235,7 +299,7 @@ class GPT2LMModel(nn.Module):
         ``kv_dtype``: "bf16" or "fp8" - the one-byte cache, half the bytes per cached token - for
         the new cache (default "bf16"); given together with a ``cache`` of the other kind it is an
         error.  ``decode_linears``: "tile" or "rows", handed to :meth:`prefill` and every
-        :meth:`decode_step`.
+        :meth:`decode_step`.  ``prefill_chunk``: :meth:`prefill`'s ``chunk`` (0: the single forward).
         The loop runs on the device; the host looks at it once every ``check_every`` steps (0:
         never), to stop early when every row has finished.
 
@@ -280,7 +344,7 @@ class GPT2LMModel(nn.Module):
             hist[:, :Lp] = input_ids
             n = lens.to(device=dev, dtype=torch.int32).clone()
             start = None if penalize_prompt else n.clone()
-        logits = self.prefill(input_ids, lens, cache, **dl)
+        logits = self.prefill(input_ids, lens, cache, **dl, **({"chunk": prefill_chunk} if prefill_chunk else {}))
         for t in range(max_new_tokens):
             if t < min_new:
                 logits[:, fill] = float("-inf")  # every live row has produced t tokens

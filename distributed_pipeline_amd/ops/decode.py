@@ -93,6 +93,25 @@ for bit; ``T = 1`` without ``counts`` is the plain kernel itself.  Anything else
 :func:`attention_decode_block_ref`, the T masked ``attention_decode_ref`` calls as written.  There is
 no table (beam) variant.
 
+A longer run of new tokens: ``attention_extend``
+------------------------------------------------
+``attention_extend(qkv_new [B, T, 3*H*D], k_cache, v_cache, lens int32 [B], n_heads, *, counts=None)
+-> out [B, T, H*D]`` for any ``T >= 1`` is ``attention_decode_block``'s rule without its limit of 8: with
+the same ``c_b``, query ``j < c_b`` stores the bits of its k and v at cache row ``lens[b] + j`` and returns
+``softmax(q_j K^T / sqrt(D)) V`` over the keys ``0 .. lens[b] + j``; query ``j >= c_b`` stores nothing and
+returns zeros; cache rows at or beyond ``lens[b] + c_b`` are neither read nor written; ``lens`` and
+``counts`` are not modified.  An empty cache (``lens[b] = 0``) is a normal case: a chunked prefill starts
+there, and a shared prefix, a second turn or a long draft go on from a warm one.
+
+bf16 on a HIP device with D in {64, 128} and ``T <= 128``: one launch of csrc/attn_extend.hip, a
+matrix-core kernel - one workgroup per (b, h, 32 queries), the 32-key tiles of the cache and of the run
+dealt round-robin to its four waves, ``S^T = K Q^T`` and ``O^T += V^T P^T`` on ``v_mfma_f32_32x32x16_bf16``
+with the weights rounded to bf16 once, the waves' states merged in wave order; no atomics, no workspace,
+two calls agree bit for bit.  Its results are those of the block kernel to the accuracy of
+``ops.nn.attention``'s forward, which rounds its weights the same way - not bit for bit.  Anything else
+(CPU, fp32, other D, a longer run, rows that are not packed): :func:`attention_extend_ref`, the
+definition in fp32 PyTorch for all queries at once.
+
 The guesses: ``lookup_draft``
 -----------------------------
 ``lookup_draft(history int64 [B, Lh], n [B], *, ngram, max_draft) -> (draft int64 [B, max_draft],
@@ -497,14 +516,16 @@ def attention_decode_fp8(qkv_new, k8, ke, v8, ve, lens, n_heads):
 BLOCK_MAX = 8  # the largest block of csrc/attn_decode_block.hip
 
 
-def _check_block(qkv_new, k_cache, lens, n_heads, counts):
+def _check_block(qkv_new, k_cache, lens, n_heads, counts, limit=BLOCK_MAX):
     if qkv_new.dim() != 3 or k_cache.dim() != 4:
         raise ValueError(f"qkv_new must be [B, T, 3*H*D] and the caches [B, H, Lmax, D], got "
                          f"{tuple(qkv_new.shape)}, {tuple(k_cache.shape)}")
     B, H, _, D = k_cache.shape
     T = qkv_new.shape[1]
-    if not 1 <= T <= BLOCK_MAX:
-        raise ValueError(f"a block holds 1 .. {BLOCK_MAX} tokens, got T = {T}")
+    if limit is None and T < 1:
+        raise ValueError(f"a run holds at least one token, got T = {T}")
+    if limit is not None and not 1 <= T <= limit:
+        raise ValueError(f"a block holds 1 .. {limit} tokens, got T = {T}")
     if H != n_heads or tuple(qkv_new.shape) != (B, T, 3 * H * D) or tuple(lens.shape) != (B,):
         raise ValueError("shapes of qkv_new, the caches, lens and n_heads do not agree")
     if counts is not None and (counts.dtype != torch.int32 or tuple(counts.shape) != (B,)):
@@ -541,6 +562,57 @@ def attention_decode_block(qkv_new, k_cache, v_cache, lens, n_heads, *, counts=N
             if out is not None:
                 return out
     return attention_decode_block_ref(qkv_new, k_cache, v_cache, lens, n_heads, counts=counts)
+
+
+# ---- attention_extend (chunked prefill, warm caches, long drafts) ---------------------------------
+
+EXTEND_MAX = 128  # the longest run of csrc/attn_extend.hip
+
+
+def attention_extend_ref(qkv_new, k_cache, v_cache, lens, n_heads, *, counts=None):
+    """The definition in fp32 PyTorch (any device, any dtype, any T >= 1), all queries at once."""
+    B, T = _check_block(qkv_new, k_cache, lens, n_heads, counts, limit=None)
+    H, Lmax, D = k_cache.shape[1:]
+    dev = qkv_new.device
+    q, k, v = qkv_new.detach().reshape(B, T, 3, H, D).unbind(2)  # [B, T, H, D] each
+    n = lens.to(dev).long()
+    c = torch.full_like(n, T) if counts is None else counts.to(dev).long()
+    c = torch.where((n >= 0) & (n < Lmax), torch.minimum(c.clamp(0, T), Lmax - n), 0)
+    pos = torch.arange(Lmax, device=dev).view(1, Lmax)
+    # the append: cache row p of row b takes token p - lens[b] where that is one of the c_b real ones
+    tok = pos - n.view(B, 1)
+    take = ((tok >= 0) & (tok < c.view(B, 1))).view(B, 1, Lmax, 1)
+    at = tok.clamp(0, T - 1).view(B, Lmax, 1, 1).expand(B, Lmax, H, D)
+    for cache, new in ((k_cache, k), (v_cache, v)):
+        cache[...] = torch.where(take, new.gather(1, at).permute(0, 2, 1, 3).to(cache.dtype), cache)
+    held = (pos < (n + c).view(B, 1)).view(B, 1, Lmax, 1)  # what lies beyond must not reach a sum
+    kf, vf = torch.where(held, k_cache.float(), 0.0), torch.where(held, v_cache.float(), 0.0)
+    j = torch.arange(T, device=dev).view(1, T)
+    live = j < c.view(B, 1)  # [B, T]
+    mask = (live.view(B, T, 1) & (pos.view(1, 1, Lmax) <= (n.view(B, 1) + j).view(B, T, 1))).view(B, 1, T, Lmax)
+    s = torch.einsum("bthd,bhld->bhtl", q.float(), kf) / math.sqrt(D)
+    p = torch.softmax(s.masked_fill(~mask, float("-inf")), -1)
+    p = torch.where(mask, p, 0.0)  # a query that is not live has no key at all
+    o = torch.einsum("bhtl,bhld->bthd", p, vf)
+    return o.to(qkv_new.dtype).reshape(B, T, H * D)
+
+
+@torch.no_grad()
+def attention_extend(qkv_new, k_cache, v_cache, lens, n_heads, *, counts=None):
+    """-> out [B, T, H*D] in ``qkv_new``'s dtype; ``k_cache`` / ``v_cache`` updated in place.  The
+    module docstring has the definition."""
+    _check_block(qkv_new, k_cache, lens, n_heads, counts, limit=None)
+    if qkv_new.is_cuda:
+        ext = get_ext()  # raises on a GPU without the built extension: no quiet fall-back
+        if ext is not None:
+            if (qkv_new.stride(-1) != 1 or qkv_new.stride(0) % 8 or qkv_new.stride(1) % 8
+                    or qkv_new.data_ptr() % 16):
+                qkv_new = qkv_new.contiguous()
+            out = ext.attn_extend(qkv_new, k_cache, v_cache, lens, int(n_heads),
+                                  None if counts is None else counts.contiguous())
+            if out is not None:
+                return out
+    return attention_extend_ref(qkv_new, k_cache, v_cache, lens, n_heads, counts=counts)
 
 
 @torch.no_grad()

@@ -42,6 +42,12 @@ decode step reads.  Its continuations are those of a slightly different model, n
 It combines with sampling, ``--noise philox``, the penalties and ``--logprobs`` and excludes
 ``--num_beams > 1`` and ``--lookahead``.  The default is ``bf16``.
 
+``--prefill_chunk N`` runs the prompts through ``GPT2LMModel.extend`` in pieces of N tokens - the
+cache-extending attention kernel ``ops.decode.attention_extend``, which appends a piece's K and V inside the
+kernel and attends it over what the cache already holds - instead of one causal forward over the padded
+prompt matrix.  The two round differently.  It excludes ``--kv_dtype fp8``, ``--num_beams > 1`` and
+``--lookahead``; with the default 0 the written file is byte for byte the one without the flag.
+
 ``--decode_linears rows`` runs the Linears of every decode step - qkv, attn_proj, mlp_fc, mlp_proj and the
 tied head - through ``ops.decode.linear_rows``, a kernel that streams each weight once for the step's few
 rows, instead of padding the rows into the training GEMM's tiles (``tile``, the default).  It applies where
@@ -124,7 +130,8 @@ def main(namespace):
                                      top_k=args.top_k, top_p=args.top_p, eos_id=eos, generator=gen,
                                      noise_seed=args.seed if args.noise == "philox" else None, row_base=n,
                                      **args.logit_processors(), **({"return_logprobs": True} if args.logprobs else {}),
-                                     **({"kv_dtype": args.kv_dtype} if args.kv_dtype != "bf16" else {}), **dl)
+                                     **({"kv_dtype": args.kv_dtype} if args.kv_dtype != "bf16" else {}), **dl,
+                                     **({"prefill_chunk": args.prefill_chunk} if args.prefill_chunk else {}))
                 toks, new_lens = res[:2]
                 if args.logprobs:
                     logprobs = res[2].cpu()

@@ -8,7 +8,9 @@ and a device copy of the bytes the fp8 step reads (2 * len * (D + 1) per (row, h
 exponent per row).
 
     python tools/attn_decode_bench.py [--B 64,8] [--lens 128,512,1023] [--H 12] [--D 64] [--reps 7] [--spread_mb 768]
-                                        [--out FILE]
+                                        [--out FILE] [--extend [--extend_shapes 0:128,512:32,896:128]]
+
+``--extend`` times the cache-extending kernel (csrc/attn_extend.hip) instead: see ``extend_shape``.
 
 Consecutive calls of a variant take different caches (and the copy different buffers), so that
 ``spread_mb`` of reads pass before one repeats and nothing is served from the last-level cache.
@@ -123,6 +125,60 @@ def shape(B, H, D, Lmax, n, reps, spread_bytes):
             "kv_bytes_fp8": nbytes8, "cache_sets_fp8": nsets8, **out}
 
 
+def extend_shape(B, H, D, Lmax, n, T, reps, spread_bytes):
+    """K-M27 (csrc/attn_extend.hip): T new tokens per row against ``n`` cached ones, beside three
+    yardsticks in the same interleaved run - ``ops.nn.attention`` on the equivalent full causal sequence
+    of n + T tokens (padded to a multiple of 64: what a prefill from scratch runs), ceil(T / 8) calls of
+    the block kernel (what the tree could append with before), and a device copy of the K/V bytes the
+    call has to read: the n cached rows and the T new ones, K and V, once per (row, head)."""
+    from distributed_pipeline_amd.ops import nn as ops
+    from distributed_pipeline_amd.ops._ext import get_ext
+    ext = get_ext(required=True)
+    g = torch.Generator(device="cuda").manual_seed(0)
+    nbytes = 2 * (n + T) * D * 2 * B * H
+    nsets = max(2, -(-spread_bytes // nbytes))
+    sets = [torch.empty(2, B, H, Lmax, D, device="cuda", dtype=torch.bfloat16).normal_(generator=g)
+            for _ in range(nsets)]
+    qkv = torch.randn(B, T, 3 * H * D, device="cuda", generator=g).bfloat16()
+    L = -(-(n + T) // 64) * 64
+    full = [torch.randn(B, L, 3 * H * D, device="cuda", generator=g).bfloat16() for _ in range(min(nsets, 8))]
+    lens = torch.full((B,), n, dtype=torch.int32, device="cuda")
+    blens = [torch.full((B,), n + j, dtype=torch.int32, device="cuda") for j in range(0, T, 8)]
+    src = [torch.empty(nbytes, dtype=torch.uint8, device="cuda").random_() for _ in range(nsets)]
+    dst = [torch.empty_like(t) for t in src]
+    turn = {"extend": 0, "attention": 0, "block": 0, "copy": 0}
+
+    def nxt(name, count=nsets):
+        turn[name] = (turn[name] + 1) % count
+        return turn[name]
+
+    def extend():
+        c = sets[nxt("extend")]
+        return ext.attn_extend(qkv, c[0], c[1], lens, H)
+
+    def attention():
+        return ops.attention(full[nxt("attention", len(full))], H, 0.0, True, False)
+
+    def block():
+        c = sets[nxt("block")]
+        for i, j in enumerate(range(0, T, 8)):
+            ext.attn_decode_block(qkv[:, j:j + 8], c[0], c[1], blens[i], H)
+
+    def copy():
+        i = nxt("copy")
+        return dst[i].copy_(src[i])
+
+    assert extend() is not None, "the extend kernel must take this shape"
+    out = interleaved({"extend": (extend, 200), "attention": (attention, 200), "block": (block, 50),
+                       "copy": (copy, 200)}, reps)
+    for name in ("attention", "block", "copy"):
+        out["extend"]["time_vs_" + name] = round(out["extend"]["median_ms"] / out[name]["median_ms"], 3)
+    # 4 (n + (T + 1) / 2) T D multiply-adds' worth of flops per (row, head): Q K^T and P V under the causal edge
+    out["extend"]["TFLOPs"] = round(4 * (n + (T + 1) / 2) * T * D * B * H / out["extend"]["median_ms"] / 1e9, 2)
+    return {"kernel": "attn_extend", "B": B, "H": H, "D": D, "Lmax": Lmax, "len": n, "T": T, "kv_bytes": nbytes,
+            "cache_sets": nsets, **out}
+
+
 def model_step(B, n, reps):
     from distributed_pipeline_amd.models import build_model
     torch.manual_seed(0)
@@ -160,11 +216,20 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--spread_mb", type=int, default=768, help="bytes read before a cache is reused, MB")
     ap.add_argument("--no_model", action="store_true")
+    ap.add_argument("--extend", action="store_true",
+                    help="the rows of the cache-extending kernel instead: B in 1,8,64 x (len, T) in --extend_shapes")
+    ap.add_argument("--extend_shapes", default="0:128,512:32,896:128")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a HIP device"
     lines = [json.dumps({"device": torch.cuda.get_device_name(0), "reps": a.reps, "torch": torch.__version__})]
-    for B in (int(x) for x in a.B.split(",")):
+    if a.extend:
+        for B in (1, 8, 64):
+            for n, T in (tuple(int(x) for x in sh.split(":")) for sh in a.extend_shapes.split(",")):
+                lines.append(json.dumps(extend_shape(B, a.H, a.D, a.Lmax, n, T, a.reps, a.spread_mb << 20)))
+                print(lines[-1], flush=True)
+        a.B, a.no_model = "", True
+    for B in (int(x) for x in a.B.split(",") if x):
         for n in (int(x) for x in a.lens.split(",")):
             lines.append(json.dumps(shape(B, a.H, a.D, a.Lmax, n, a.reps, a.spread_mb << 20)))
             print(lines[-1], flush=True)
