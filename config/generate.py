@@ -92,6 +92,11 @@ class ContinueSettings(S):
                "pieces of this many tokens instead of one causal forward over the padded prompt matrix; 0 = off. "
                "The two round differently, so continuations can differ. Excludes --kv_dtype fp8, --num_beams > 1 "
                "and --lookahead.")
+    num_samples: int \
+        = _(1, "Continuations sampled per prompt (1 = off). Above 1 the prompt's forward runs once and its keys are "
+               "cached once for all of them (GPT2LMModel.generate_samples), and every output line gains 'samples'; "
+               "'continuation' is sample 0. Needs --temperature > 0 and excludes --num_beams > 1, --lookahead, "
+               "--kv_dtype fp8, --prefill_chunk, the penalties, --min_new_tokens and --logprobs.")
     out_path: str \
         = _("", "Output .jsonl file (default: generated_<checkpoint>_seed<seed>.jsonl next to the checkpoint).")
     precision: Choice("bf16", "fp32") \
@@ -193,6 +198,21 @@ class GenerateSettings(
         if self.logprobs and (self.num_beams > 1 or self.lookahead):
             raise ValueError("--logprobs comes from generate's own loop: it excludes --num_beams > 1 (see "
                              "--keep_beams for beam scores) and --lookahead")
+        if self.num_samples < 1:
+            raise ValueError(f"--num_samples must be >= 1, got {self.num_samples}")
+        if self.num_samples > 1:
+            if self.num_beams > 1 or self.lookahead > 0 or self.kv_dtype == "fp8" or self.prefill_chunk > 0:
+                raise ValueError("--num_samples > 1 runs generate_samples' own loop over a shared bf16 prompt cache: "
+                                 "it excludes --num_beams > 1, --lookahead, --kv_dtype fp8 and --prefill_chunk")
+            if self.logprobs or self.logit_processors() != dict(
+                    repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, no_repeat_ngram=0,
+                    min_new_tokens=0, penalize_prompt=True):
+                raise ValueError("--num_samples > 1 excludes --repetition_penalty, --presence_penalty, "
+                                 "--frequency_penalty, --no_repeat_ngram, --min_new_tokens, --penalize_prompt and "
+                                 "--logprobs")
+            if self.temperature == 0:
+                raise ValueError("--num_samples > 1 with --temperature 0 would write the same continuation "
+                                 f"{self.num_samples} times")
         if self.prompt_len < 1 or self.max_new_tokens < 1:
             raise ValueError("--prompt_len and --max_new_tokens must be >= 1")
         if self.prompt_len + self.max_new_tokens > self.seq_len:

@@ -213,6 +213,53 @@ static c10::optional<at::Tensor> attn_extend(const at::Tensor& qkv_new, at::Tens
   return attn_block_any(qkv_new, k_cache, v_cache, lens, n_heads, counts, true);
 }
 
+// One decode step of B groups of `group` rows over a shared prefix cache (csrc/attn_decode_grouped.hip):
+// qkv_new [R, 3 H D] bf16, kp / vp [B, H, Lp, D] bf16 (read only), plens int32 [B], ks / vs [R, H, Ls, D] bf16
+// (updated in place), slens int32 [R], R = B group -> out [R, H D] bf16 (launchers.h has the rule), or None
+// for a case the kernel does not cover.  qs: queries per workgroup (4, 8, 16, 32; 0: the launcher's choice).
+static c10::optional<at::Tensor> attn_decode_grouped(const at::Tensor& qkv_new, const at::Tensor& kp,
+                                                     const at::Tensor& vp, const at::Tensor& plens, at::Tensor& ks,
+                                                     at::Tensor& vs, const at::Tensor& slens, int64_t n_heads,
+                                                     int64_t group, int64_t qs) {
+  TORCH_CHECK(qkv_new.dim() == 2 && kp.dim() == 4 && vp.dim() == 4 && ks.dim() == 4 && vs.dim() == 4 &&
+                  plens.dim() == 1 && slens.dim() == 1 && n_heads > 0,
+              "attn_decode_grouped: qkv_new [R, 3 H D], prefix [B, H, Lp, D], plens [B], suffix [R, H, Ls, D], slens [R]");
+  const int64_t B = kp.size(0), H = kp.size(1), Lp = kp.size(2), D = kp.size(3), R = ks.size(0), Ls = ks.size(2);
+  TORCH_CHECK(group >= 1, "attn_decode_grouped: group must be >= 1, got ", group);
+  TORCH_CHECK(R == B * group, "attn_decode_grouped: ", R, " suffix rows are not ", B, " groups of ", group);
+  TORCH_CHECK(H == n_heads && vp.sizes() == kp.sizes() && vs.sizes() == ks.sizes() && ks.size(1) == H &&
+                  ks.size(3) == D && qkv_new.size(0) == R && qkv_new.size(1) == 3 * H * D && plens.size(0) == B &&
+                  slens.size(0) == R,
+              "attn_decode_grouped: shapes of qkv_new, the caches, plens, slens and n_heads do not agree");
+  TORCH_CHECK(plens.scalar_type() == at::kInt && slens.scalar_type() == at::kInt,
+              "attn_decode_grouped: plens and slens must be int32");
+  TORCH_CHECK(qs == 0 || qs == 4 || qs == 8 || qs == 16 || qs == 32, "attn_decode_grouped: qs must be 0, 4, 8, 16 or 32");
+  for (const at::Tensor* t : {&qkv_new, &kp, &vp, &plens, (const at::Tensor*)&ks, (const at::Tensor*)&vs, &slens})
+    if (!t->is_cuda() || t->device() != qkv_new.device()) return c10::nullopt;
+  for (const at::Tensor* t : {&qkv_new, &kp, &vp, (const at::Tensor*)&ks, (const at::Tensor*)&vs})
+    if (t->scalar_type() != at::kBFloat16) return c10::nullopt;
+  if ((D != 64 && D != 128) || group > 32 || B == 0 || Lp == 0 || Ls == 0 || Lp > 0x7fffffffLL || Ls > 0x7fffffffLL ||
+      R * H > 0x7fffffffLL)
+    return c10::nullopt;
+  auto rows_ok = [&](const at::Tensor& c) {  // packed rows of D; 16-byte row starts
+    return c.stride(3) == 1 && c.stride(2) == D && c.stride(0) % 8 == 0 && c.stride(1) % 8 == 0 &&
+           reinterpret_cast<uintptr_t>(c.data_ptr()) % 16 == 0;
+  };
+  if (!rows_ok(kp) || !rows_ok(vp) || !rows_ok(ks) || !rows_ok(vs) || !plens.is_contiguous() || !slens.is_contiguous())
+    return c10::nullopt;
+  if (qkv_new.stride(1) != 1 || qkv_new.stride(0) % 8 != 0 || reinterpret_cast<uintptr_t>(qkv_new.data_ptr()) % 16 != 0)
+    return c10::nullopt;
+  const c10::DeviceGuard guard(qkv_new.device());
+  at::Tensor out = at::empty({R, H * D}, qkv_new.options());
+  const bool ok = dpa::launch_attn_decode_grouped(
+      bf_ptr(qkv_new), qkv_new.stride(0), bf_ptr(kp), bf_ptr(vp), kp.stride(0), kp.stride(1), vp.stride(0),
+      vp.stride(1), plens.data_ptr<int>(), (int)Lp, bf_mut(ks), bf_mut(vs), ks.stride(0), ks.stride(1), vs.stride(0),
+      vs.stride(1), slens.data_ptr<int>(), (int)Ls, (int)B, (int)group, (int)H, (int)D, (int)qs, bf_mut(out),
+      cur_stream());
+  if (!ok) return c10::nullopt;
+  return out;
+}
+
 // The decode step over a one-byte cache (csrc/attn_decode_fp8.hip): qkv_new [B, 3 H D] bf16, k8 / v8 uint8
 // [B, H, Lmax, D], ke / ve int8 [B, H, Lmax] (all four updated in place at row lens[b]), lens [B] int32
 // -> out [B, H D] bf16, or None for a case the kernel does not cover: the caller's PyTorch path takes it.
@@ -353,6 +400,12 @@ void dpa::register_attention(pybind11::module& m) {
         "KV-cache append + attention of a run of T <= 128 new tokens per row on the MFMA (attn_decode_block's rule) -> out [B, T, H D] bf16 | None (case not covered)",
         py::arg("qkv_new"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"), py::arg("n_heads"),
         py::arg("counts") = py::none());
+  m.def("attn_decode_grouped", &attn_decode_grouped,
+        "one decode step of B groups of `group` rows: a prefix cache per group (read only) + a suffix cache per row (appended to) on the MFMA -> out [R, H D] bf16 | None (case not covered)",
+        py::arg("qkv_new"), py::arg("kp"), py::arg("vp"), py::arg("plens"), py::arg("ks"), py::arg("vs"),
+        py::arg("slens"), py::arg("n_heads"), py::arg("group"), py::arg("qs") = 0);
+  m.def("attn_decode_grouped_qs", &dpa::attn_decode_grouped_qs,
+        "queries per workgroup attn_decode_grouped picks for (B H, group, compute units)");
   m.def("attn_decode_fp8", &attn_decode_fp8,
         "attn_decode over a one-byte cache (e4m3fn codes + one int8 exponent per row): quantizing append + single-query attention -> out [B, H D] bf16 | None (case not covered)",
         py::arg("qkv_new"), py::arg("k8"), py::arg("ke"), py::arg("v8"), py::arg("ve"), py::arg("lens"),

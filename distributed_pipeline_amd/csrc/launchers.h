@@ -282,6 +282,26 @@ bool launch_attn_extend(const uint16_t* qkv_new, int64_t qkv_sb, int64_t qkv_st,
                         uint16_t* v_cache, int64_t k_sb, int64_t k_sh, int64_t v_sb, int64_t v_sh, const int* lens,
                         const int* counts, int B, int T, int H, int Lmax, int D, uint16_t* out, hipStream_t s);
 
+// ---- attn_decode_grouped.hip: one decode step of B groups of G rows over a shared prefix cache (K-M28) ----
+// Row r = b G + g has the prefix keys of group b (kp / vp rows of D at b * sb + h * sh + key * D, plens [B]
+// int32) and a suffix cache of its own (ks / vs at r * sb + h * sh + key * D, slens [B G] int32); qkv_new
+// [B G][3][H][D] bf16 with rows qkv_sb apart, out [B G][H][D] bf16.  Row r is active iff 0 <= slens[r] < Ls and
+// 0 <= plens[b] <= Lp: it stores the bits of its k and v at suffix row slens[r] and attends over the prefix keys
+// 0 .. plens[b] - 1, its suffix keys 0 .. slens[r] - 1 and the new key (from qkv_new); any other row stores
+// nothing and returns zeros.  The prefix is never written, plens and slens are not modified, prefix rows at or
+// beyond plens[b] and suffix rows at or beyond slens[r] are never loaded.  The weights are rounded to bf16
+// before they meet V (launch_attn_extend's accuracy).  qs: queries of a group per workgroup, one of 4, 8, 16,
+// 32, or 0 for attn_decode_grouped_qs's choice; a row's bits depend neither on it nor on the other rows.
+// One launch of B H ceil(G / qs) workgroups, no workspace, no atomics: two calls agree bit for bit.  false,
+// with no launch: as launch_attn_decode for either cache, G outside 1 .. 32, or another qs.
+bool launch_attn_decode_grouped(const uint16_t* qkv_new, int64_t qkv_sb, const uint16_t* kp, const uint16_t* vp,
+                                int64_t kp_sb, int64_t kp_sh, int64_t vp_sb, int64_t vp_sh, const int* plens, int Lp,
+                                uint16_t* ks, uint16_t* vs, int64_t ks_sb, int64_t ks_sh, int64_t vs_sb,
+                                int64_t vs_sh, const int* slens, int Ls, int B, int G, int H, int D, int qs,
+                                uint16_t* out, hipStream_t s);
+// The largest of 32, 16, 8 that still gives BH ceil(G / qs) >= ncu workgroups, else 4.
+int attn_decode_grouped_qs(int64_t BH, int G, int ncu);
+
 // ---- linear_rows.hip: the Linears of a decode step, 1 .. 128 rows against a whole weight (K-M26) ----
 // y[m][n] = bf16(act(sum_k x[m][k] W[n][k] + bias[n])): x [M][K], W [N][K] and y [M][N] bf16 with rows ldx, ldw
 // and ldy elements apart, bias [N] bf16 or null, act a code of act.h (0 .. 3); fp32 products, sums, bias add

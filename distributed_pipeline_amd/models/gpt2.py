@@ -245,7 +245,8 @@ class GPT2LMModel(nn.Module):
         does no cache work, keeps its ``lens``, and its logits mean nothing.  ``table``: a pair
         ``(src uint8 [B, max_len], beams)`` handed to ``attention_decode`` - the rows are groups
         of ``beams`` slots that read their cached keys through ``src`` (beam search; not over an
-        fp8 cache).  Over an fp8 cache the step is ``ops.decode.attention_decode_fp8``.
+        fp8 cache).  Over an fp8 cache the step is ``ops.decode.attention_decode_fp8``.  Over a
+        :class:`GroupKVCache` (several continuations per prompt) it is :meth:`_decode_step_grouped`.
 
         ``decode_linears``: "tile" (the default) runs the Linears through ``ops.linear``, the B rows
         padded into the training GEMM's tiles.  "rows" runs qkv, attn_proj, mlp_fc with its GELU,
@@ -254,6 +255,10 @@ class GPT2LMModel(nn.Module):
         computes in bf16 on a HIP device; anywhere else it is "tile".  The residual adds, the
         LayerNorms and the attention are the same in both.  The two modes round differently."""
         from ..ops.decode import attention_decode, attention_decode_fp8
+        if isinstance(cache, GroupKVCache):
+            if table is not None:
+                raise ValueError("a GroupKVCache has no indirection-table variant")
+            return self._decode_step_grouped(tokens, cache, decode_linears)
         if cache.fp8 and table is not None:
             raise ValueError("an fp8 cache has no indirection-table variant: beam search needs kv_dtype='bf16'")
         dt = self.compute_dtype
@@ -374,6 +379,110 @@ class GPT2LMModel(nn.Module):
             logits = self.decode_step(tok, cache, **dl)
         cache.lens.masked_fill_(done, -1)
         return (out, new_lens, logprobs) if return_logprobs else (out, new_lens)
+
+    # ---- several samples per prompt over a shared prompt cache (inference only) ---------------
+
+    def init_group_cache(self, batch, group, prompt_len, max_new, device=None, dtype=None, kv_dtype="bf16"):
+        """An empty :class:`GroupKVCache` for ``batch`` prompts of up to ``prompt_len`` tokens with ``group``
+        continuations each of up to ``max_new`` tokens: a ``prefix`` cache of ``batch`` rows, which
+        :meth:`prefill` fills once per prompt, and a ``suffix`` cache of ``batch * group`` rows (row
+        ``b * group + g``), which :meth:`decode_step` appends to.  Values in ``dtype`` (the compute dtype);
+        there is no fp8 variant."""
+        if kv_dtype != "bf16":
+            raise ValueError(f"a group cache has no fp8 variant: it needs kv_dtype='bf16', got {kv_dtype!r}")
+        if group < 1 or max_new < 1:
+            raise ValueError(f"group and max_new must be >= 1, got {group}, {max_new}")
+        room = self.cfg["max_position_embeddings"] - prompt_len  # a continuation ends with the model's positions
+        return GroupKVCache(self.init_cache(batch, prompt_len, device, dtype),
+                            self.init_cache(batch * group, max(1, min(max_new, room)), device, dtype), group)
+
+    def _decode_step_grouped(self, tokens, cache, decode_linears):
+        """:meth:`decode_step` over a :class:`GroupKVCache`: row ``r = b G + g`` stands at position
+        ``prefix.lens[b] + suffix.lens[r]``, every layer's attention is
+        ``ops.decode.attention_decode_grouped`` and ``suffix.lens`` advances on the device.  A parked row
+        (``suffix.lens`` outside 0 .. its max_len - 1) does no cache work and keeps its ``lens``."""
+        from ..ops.decode import attention_decode_grouped
+        dt = self.compute_dtype
+        pre, suf, G = cache.prefix, cache.suffix, cache.group
+        R = tokens.shape[0]
+        if R != suf.batch:
+            raise ValueError(f"{R} tokens do not fit a group cache of {pre.batch} x {G} rows")
+        rows = self._rows(decode_linears, R, tokens)
+        heads = suf.heads
+        plens = pre.lens.view(-1, 1)  # against [B, G] views of the rows: no repeated copy
+        pos = (plens + suf.lens.view(-1, G)).view(R).long().clamp(0, self.cfg["max_position_embeddings"] - 1)
+        ln0 = self.h[0].ln_1
+        x, a = ops.residual_layernorm(self.wte(tokens.view(1, R), dt), None, ln0.weight, ln0.bias, 0.0, ln0.eps,
+                                      False, pos=self.wpe(pos, dt))
+
+        def attend(i, qkv):
+            return attention_decode_grouped(qkv.view(R, -1), pre.k[i], pre.v[i], pre.lens, suf.k[i], suf.v[i],
+                                            suf.lens, heads, group=G).view(1, R, -1)
+
+        a = self._blocks(x, a, attend, rows)
+        slens = suf.lens.view(-1, G)
+        slens += ((slens >= 0) & (slens < suf.max_len) & ((plens >= 0) & (plens <= pre.max_len))).to(slens.dtype)
+        return self._head(a.view(R, -1), rows)
+
+    @torch.no_grad()
+    def generate_samples(self, input_ids, lens, max_new_tokens, *, num_samples, temperature=1.0, top_k=0, top_p=0.0,
+                         eos_id=None, generator=None, noise_seed=None, row_base=0, decode_linears="tile",
+                         cache=None, check_every=16):
+        """``num_samples = G`` continuations of every right-padded prompt -> (tokens [B, G, max_new_tokens],
+        new_lens [B, G]), with :meth:`generate`'s loop and meanings over a :class:`GroupKVCache`: the prompt's
+        forward runs once per prompt, its keys are cached once, and every decode step reads them once per
+        group (``ops.decode.attention_decode_grouped``).
+
+        The first token of all G samples is drawn from the one prefill logits row of the prompt.  With an
+        integer ``noise_seed`` sample (b, g) draws with the global row ``row_base + b G + g`` - the row it
+        would have in :meth:`generate` on the prompts repeated G times each, so the noise is the same.  A row
+        stops when it has emitted ``eos_id``, its suffix cache is full or the model's positions end: it is
+        parked (``cache.suffix.lens[r] = -1``) and the rest of its output is ``eos_id`` (0 without one).
+        ``cache``: one from :meth:`init_group_cache` to use.  Penalties, log-probabilities, beams and
+        lookahead are :meth:`generate`'s, :meth:`beam_search`'s and :meth:`generate_lookahead`'s alone."""
+        from utils.lm_sampling import sample_next
+        from ..ops.decode import sample_tokens
+        G = int(num_samples)
+        if G < 1:
+            raise ValueError(f"num_samples must be >= 1, got {num_samples}")
+        philox = noise_seed is not None and temperature > 0
+        B, Lp = input_ids.shape
+        R = B * G
+        dev = input_ids.device
+        self._rows(decode_linears, R, input_ids)  # an unknown value raises here
+        dl = {} if decode_linears == "tile" else {"decode_linears": decode_linears}
+        if cache is None:
+            cache = self.init_group_cache(B, G, Lp, max_new_tokens, dev)
+        elif cache.group != G or cache.prefix.batch != B:
+            raise ValueError(f"the given cache holds {cache.prefix.batch} groups of {cache.group}, not {B} of {G}")
+        pre, suf = cache.prefix, cache.suffix
+        fill = 0 if eos_id is None else int(eos_id)
+        out = torch.full((R, max_new_tokens), fill, dtype=torch.long, device=dev)
+        new_lens = torch.zeros(R, dtype=torch.long, device=dev)
+        done = torch.zeros(R, dtype=torch.bool, device=dev)
+        suf.lens.zero_()
+        logits = self.prefill(input_ids, lens, pre, **dl).repeat_interleave(G, 0)
+        last_pos = self.cfg["max_position_embeddings"] - pre.lens.repeat_interleave(G)  # suffix keys the positions allow
+        for t in range(max_new_tokens):
+            if philox:
+                tok = sample_tokens(logits, temperature=temperature, top_k=top_k, top_p=top_p, seed=int(noise_seed),
+                                    step=t, row_base=row_base)
+            else:
+                tok = sample_next(logits, temperature, top_k, top_p, generator)
+            tok = torch.where(done, fill, tok)
+            out[:, t] = tok
+            new_lens += (~done).to(new_lens.dtype)
+            if eos_id is not None:
+                done = done | (tok == fill)
+            done = done | (suf.lens >= suf.max_len) | (suf.lens >= last_pos)  # no room to run this token
+            if t + 1 == max_new_tokens:
+                break
+            suf.lens.masked_fill_(done, -1)
+            if check_every and (t + 1) % check_every == 0 and bool(done.all()):
+                break
+            logits = self.decode_step(tok, cache, **dl)
+        suf.lens.masked_fill_(done, -1)
+        return out.view(B, G, max_new_tokens), new_lens.view(B, G)
 
     # ---- teacher-forced scoring (inference only) -----------------------------------------
 
@@ -774,6 +883,21 @@ class KVCache:
         view.lens = self.lens[slot::beams]
         view.table = None
         return view
+
+
+class GroupKVCache:
+    """The cache of ``GPT2LMModel.generate_samples``: ``prefix``, a :class:`KVCache` of B rows that holds each
+    prompt's keys and values once, and ``suffix``, one of ``B * group`` rows (row ``b * group + g``) for what
+    each of the prompt's ``group`` continuations has produced since.  Row r's tokens are
+    ``prefix.lens[r // group] + suffix.lens[r]``; ``suffix.lens[r]`` outside 0 .. ``suffix.max_len - 1`` parks
+    the row."""
+
+    def __init__(self, prefix, suffix, group):
+        if prefix.fp8 or suffix.fp8:
+            raise ValueError("a group cache has no fp8 variant")
+        if suffix.batch != prefix.batch * group:
+            raise ValueError(f"{suffix.batch} suffix rows are not {prefix.batch} groups of {group}")
+        self.prefix, self.suffix, self.group = prefix, suffix, int(group)
 
 
 def _gpt2_train_flops_per_sample(self, seq_len):

@@ -112,6 +112,33 @@ two calls agree bit for bit.  Its results are those of the block kernel to the a
 (CPU, fp32, other D, a longer run, rows that are not packed): :func:`attention_extend_ref`, the
 definition in fp32 PyTorch for all queries at once.
 
+Several samples of one prompt: ``attention_decode_grouped``
+-----------------------------------------------------------
+``attention_decode_grouped(qkv_new [R, 3*H*D], kp, vp [B, H, Lp, D], plens int32 [B], ks, vs [R, H, Ls, D],
+slens int32 [R], n_heads, *, group) -> out [R, H*D]`` is one decode step of ``R = B G`` rows, ``G = group``,
+where the G rows ``r = b G + g`` of a group continue one prompt: the prompt's keys and values are held
+once per group (the prefix cache ``kp`` / ``vp`` with ``plens``) and every row has a cache of its own for the
+tokens it has produced since (the suffix cache ``ks`` / ``vs`` with ``slens``).
+
+* Row r is active iff ``0 <= slens[r] < Ls`` and ``0 <= plens[b] <= Lp``.
+* An active row stores its new k and v (the bits of ``qkv_new``) at ``ks / vs[r, :, slens[r]]`` and returns
+  ``softmax(q K^T / sqrt(D)) V``, rounded once to the dtype, over three sets of keys in this order: the
+  prefix keys ``kp[b, :, 0 .. plens[b] - 1]``, its own suffix keys ``ks[r, :, 0 .. slens[r] - 1]``, and the
+  new key, taken from ``qkv_new`` and never read back.
+* An inactive row stores nothing and returns zeros.
+* ``kp`` and ``vp`` are never written; ``plens`` and ``slens`` are not modified (the caller advances
+  ``slens``); prefix rows at or beyond ``plens[b]`` and suffix rows at or beyond ``slens[r]`` are never read,
+  whatever they hold.  ``plens[b] = 0`` is legal: the row attends over its suffix and the new key.
+
+bf16 on a HIP device with D in {64, 128}, ``1 <= G <= 32`` and cache rows packed on 16 bytes: one launch of
+csrc/attn_decode_grouped.hip, a matrix-core kernel - one workgroup per (b, h, slice of up to 32 queries of
+the group), so a prefix key is loaded once per slice and scored against all of its queries as the B
+columns of ``v_mfma_f32_32x32x16_bf16``; the rows' own suffix tiles and their new keys go through the same
+tile routine with every other column masked; the weights are rounded to bf16 once (``attention_extend``'s
+accuracy); no atomics, no workspace.  Two calls agree bit for bit, and a row's bits depend neither on the
+slice size nor on what the other rows of the call hold.  Anything else (CPU, fp32, other D, a larger G,
+rows that are not packed): :func:`attention_decode_grouped_ref`, the definition in fp32 PyTorch.
+
 The guesses: ``lookup_draft``
 -----------------------------
 ``lookup_draft(history int64 [B, Lh], n [B], *, ngram, max_draft) -> (draft int64 [B, max_draft],
@@ -613,6 +640,78 @@ def attention_extend(qkv_new, k_cache, v_cache, lens, n_heads, *, counts=None):
             if out is not None:
                 return out
     return attention_extend_ref(qkv_new, k_cache, v_cache, lens, n_heads, counts=counts)
+
+
+# ---- attention_decode_grouped (several samples of one prompt over a shared prefix cache) ------------
+
+GROUP_MAX = 32  # the largest group of csrc/attn_decode_grouped.hip
+
+
+def _check_grouped(qkv_new, kp, vp, plens, ks, vs, slens, n_heads, group):
+    G = int(group)
+    if G < 1:
+        raise ValueError(f"group must be >= 1, got {group}")
+    if qkv_new.dim() != 2 or kp.dim() != 4 or ks.dim() != 4:
+        raise ValueError(f"qkv_new must be [R, 3*H*D], the prefix [B, H, Lp, D] and the suffix [R, H, Ls, D], got "
+                         f"{tuple(qkv_new.shape)}, {tuple(kp.shape)}, {tuple(ks.shape)}")
+    B, H, _, D = kp.shape
+    R = ks.shape[0]
+    if R != B * G:
+        raise ValueError(f"{R} suffix rows are not {B} groups of {G}")
+    if (H != n_heads or vp.shape != kp.shape or vs.shape != ks.shape or ks.shape[1] != H or ks.shape[3] != D
+            or tuple(qkv_new.shape) != (R, 3 * H * D) or tuple(plens.shape) != (B,) or tuple(slens.shape) != (R,)):
+        raise ValueError("shapes of qkv_new, the caches, plens, slens and n_heads do not agree")
+    if plens.dtype != torch.int32 or slens.dtype != torch.int32:
+        raise ValueError(f"plens and slens must be int32, got {plens.dtype}, {slens.dtype}")
+    return B, G, R
+
+
+def attention_decode_grouped_ref(qkv_new, kp, vp, plens, ks, vs, slens, n_heads, *, group):
+    """The definition in fp32 PyTorch (any device, any dtype)."""
+    B, G, R = _check_grouped(qkv_new, kp, vp, plens, ks, vs, slens, n_heads, group)
+    H, Lp, D = kp.shape[1:]
+    Ls = ks.shape[2]
+    dev = qkv_new.device
+    q, k, v = qkv_new.detach().reshape(R, 3, H, D).unbind(1)
+    rows = torch.arange(R, device=dev)
+    grp = rows // G
+    pn, sn = plens.to(dev).long()[grp], slens.to(dev).long()
+    active = (sn >= 0) & (sn < Ls) & (pn >= 0) & (pn <= Lp)
+    at = sn.clamp(0, Ls - 1)
+    keep = active.view(R, 1, 1)
+    # the append: an inactive row writes back what its slot already holds
+    ks[rows, :, at] = torch.where(keep, k.to(ks.dtype), ks[rows, :, at])
+    vs[rows, :, at] = torch.where(keep, v.to(vs.dtype), vs[rows, :, at])
+    # prefix keys below plens, then suffix keys up to the one just appended (its bits are qkv_new's)
+    pmask = (torch.arange(Lp, device=dev).view(1, Lp) < pn.view(R, 1)) & active.view(R, 1)
+    smask = (torch.arange(Ls, device=dev).view(1, Ls) <= at.view(R, 1)) & active.view(R, 1)
+    mask = torch.cat([pmask, smask], 1).view(R, 1, Lp + Ls)
+    held = mask.unsqueeze(-1)  # what lies beyond must not reach a sum
+    kf = torch.where(held, torch.cat([kp[grp], ks], 2).float(), 0.0)
+    vf = torch.where(held, torch.cat([vp[grp], vs], 2).float(), 0.0)
+    s = torch.einsum("rhd,rhld->rhl", q.float(), kf) / math.sqrt(D)
+    p = torch.softmax(s.masked_fill(~mask, float("-inf")), -1)
+    p = torch.where(mask, p, 0.0)  # an inactive row has no key at all
+    o = torch.einsum("rhl,rhld->rhd", p, vf)
+    return o.to(qkv_new.dtype).reshape(R, H * D)
+
+
+@torch.no_grad()
+def attention_decode_grouped(qkv_new, kp, vp, plens, ks, vs, slens, n_heads, *, group, qs=0):
+    """-> out [R, H*D] in ``qkv_new``'s dtype; ``ks`` / ``vs`` updated in place.  The module docstring has the
+    definition.  ``qs``: the kernel's queries per workgroup (4, 8, 16, 32; 0: its own choice) - a tuning knob
+    for measurements, the result's bits do not depend on it."""
+    _check_grouped(qkv_new, kp, vp, plens, ks, vs, slens, n_heads, group)
+    if qkv_new.is_cuda:
+        ext = get_ext()  # raises on a GPU without the built extension: no quiet fall-back
+        if ext is not None:
+            if qkv_new.stride(-1) != 1 or qkv_new.stride(0) % 8 or qkv_new.data_ptr() % 16:
+                qkv_new = qkv_new.contiguous()
+            out = ext.attn_decode_grouped(qkv_new, kp, vp, plens.contiguous(), ks, vs, slens.contiguous(),
+                                          int(n_heads), int(group), int(qs))
+            if out is not None:
+                return out
+    return attention_decode_grouped_ref(qkv_new, kp, vp, plens, ks, vs, slens, n_heads, group=group)
 
 
 @torch.no_grad()

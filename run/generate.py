@@ -48,6 +48,15 @@ kernel and attends it over what the cache already holds - instead of one causal 
 prompt matrix.  The two round differently.  It excludes ``--kv_dtype fp8``, ``--num_beams > 1`` and
 ``--lookahead``; with the default 0 the written file is byte for byte the one without the flag.
 
+``--num_samples G`` (G > 1) runs ``GPT2LMModel.generate_samples``: G sampled continuations per prompt from one
+prefill and one cached copy of the prompt's keys, which every decode step reads once per prompt
+(``ops.decode.attention_decode_grouped``) where G repeated prompts would read them G times.  Each line gains
+``samples``, the G id lists cut like ``continuation``, which is sample 0.  Under ``--noise philox`` sample g of
+the split's i-th prompt draws with row ``i G + g``, so the file does not depend on ``--batch_size``.  It needs
+``--temperature`` above 0 and excludes ``--num_beams > 1``, ``--lookahead``, ``--kv_dtype fp8``,
+``--prefill_chunk``, the penalties, ``--min_new_tokens`` and ``--logprobs``; with the default 1 the written file
+is byte for byte the one without the flag.
+
 ``--decode_linears rows`` runs the Linears of every decode step - qkv, attn_proj, mlp_fc, mlp_proj and the
 tied head - through ``ops.decode.linear_rows``, a kernel that streams each weight once for the step's few
 rows, instead of padding the rows into the training GEMM's tiles (``tile``, the default).  It applies where
@@ -125,6 +134,13 @@ def main(namespace):
                 for key, val in stats.items():
                     look[key] += val
                 look["tokens"] += int(new_lens.sum())
+            elif args.num_samples > 1:
+                samples, sample_lens = model.generate_samples(
+                    ids[:, :Lp].contiguous(), lens, Ln, num_samples=args.num_samples, temperature=args.temperature,
+                    top_k=args.top_k, top_p=args.top_p, eos_id=eos, generator=gen,
+                    noise_seed=args.seed if args.noise == "philox" else None, row_base=n * args.num_samples, **dl)
+                samples, sample_lens = samples.cpu(), sample_lens.cpu()
+                toks, new_lens = samples[:, 0], sample_lens[:, 0]
             else:
                 res = model.generate(ids[:, :Lp].contiguous(), lens, Ln, temperature=args.temperature,
                                      top_k=args.top_k, top_p=args.top_p, eos_id=eos, generator=gen,
@@ -149,6 +165,8 @@ def main(namespace):
                     live = [w for w in range(args.num_beams) if beam_scores[i, w] > float("-inf")]
                     line["beams"] = [cut(beams[i, w], beam_lens[i, w]) for w in live]
                     line["beam_scores"] = [float(beam_scores[i, w]) for w in live]
+                if args.num_samples > 1:
+                    line["samples"] = [cut(samples[i, g], sample_lens[i, g]) for g in range(args.num_samples)]
                 if args.logprobs:
                     line["logprobs"] = [float(x) for x in logprobs[i, :len(line["continuation"])]]
                 fout.write(json.dumps(line) + "\n")

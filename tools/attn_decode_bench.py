@@ -8,9 +8,10 @@ and a device copy of the bytes the fp8 step reads (2 * len * (D + 1) per (row, h
 exponent per row).
 
     python tools/attn_decode_bench.py [--B 64,8] [--lens 128,512,1023] [--H 12] [--D 64] [--reps 7] [--spread_mb 768]
-                                        [--out FILE] [--extend [--extend_shapes 0:128,512:32,896:128]]
+                                        [--out FILE] [--extend [--extend_shapes 0:128,512:32,896:128]] [--grouped]
 
 ``--extend`` times the cache-extending kernel (csrc/attn_extend.hip) instead: see ``extend_shape``.
+``--grouped`` times the grouped decode kernel (csrc/attn_decode_grouped.hip) instead: see ``grouped_shape``.
 
 Consecutive calls of a variant take different caches (and the copy different buffers), so that
 ``spread_mb`` of reads pass before one repeats and nothing is served from the last-level cache.
@@ -179,6 +180,81 @@ def extend_shape(B, H, D, Lmax, n, T, reps, spread_bytes):
             "cache_sets": nsets, **out}
 
 
+def grouped_shape(R, G, H, D, prefix, suffix, reps, spread_bytes):
+    """K-M28 (csrc/attn_decode_grouped.hip): R = B G rows, ``prefix`` shared keys per group and ``suffix`` own keys per
+    row, beside two yardsticks in the same interleaved run - K-M18 (csrc/attn_decode.hip) on R rows that each hold
+    a full copy of prefix + suffix (what G samples of a prompt cost without the kernel), and a device copy of the
+    K/V bytes K-M28 has to read: the prefix once per group, the suffix once per row."""
+    from distributed_pipeline_amd.ops._ext import get_ext
+    ext = get_ext(required=True)
+    g = torch.Generator(device="cuda").manual_seed(0)
+    B = R // G
+    nbytes = 2 * D * 2 * H * (B * prefix + R * suffix)   # K-M28's reads
+    nbytes_rows = 2 * D * 2 * H * R * (prefix + suffix)  # K-M18's
+    nsets, nsets_rows = max(2, -(-spread_bytes // nbytes)), max(2, -(-spread_bytes // nbytes_rows))
+    new = lambda *shape: torch.empty(*shape, device="cuda", dtype=torch.bfloat16).normal_(generator=g)  # noqa: E731
+    pre, suf = [new(2, B, H, prefix, D) for _ in range(nsets)], [new(2, R, H, suffix + 1, D) for _ in range(nsets)]
+    full = [new(2, R, H, prefix + suffix + 1, D) for _ in range(nsets_rows)]
+    qkv = torch.randn(R, 3 * H * D, device="cuda", generator=g).bfloat16()
+    plens = torch.full((B,), prefix, dtype=torch.int32, device="cuda")
+    slens = torch.full((R,), suffix, dtype=torch.int32, device="cuda")
+    lens = torch.full((R,), prefix + suffix, dtype=torch.int32, device="cuda")
+    src = [torch.empty(nbytes, dtype=torch.uint8, device="cuda").random_() for _ in range(nsets)]
+    dst = [torch.empty_like(t) for t in src]
+    turn = {"grouped": 0, "rows": 0, "copy": 0}
+
+    def nxt(name, count):
+        turn[name] = (turn[name] + 1) % count
+        return turn[name]
+
+    def grouped():
+        i = nxt("grouped", nsets)
+        return ext.attn_decode_grouped(qkv, pre[i][0], pre[i][1], plens, suf[i][0], suf[i][1], slens, H, G)
+
+    def rows():
+        c = full[nxt("rows", nsets_rows)]
+        return ext.attn_decode(qkv, c[0], c[1], lens, H)
+
+    def copy():
+        i = nxt("copy", nsets)
+        return dst[i].copy_(src[i])
+
+    assert grouped() is not None, "the grouped kernel must take this shape"
+    out = interleaved({"grouped": (grouped, 300), "rows": (rows, 300), "copy": (copy, 300)}, reps)
+    out["grouped"]["time_vs_rows"] = round(out["grouped"]["median_ms"] / out["rows"]["median_ms"], 3)
+    out["grouped"]["time_vs_copy"] = round(out["grouped"]["median_ms"] / out["copy"]["median_ms"], 3)
+    qs = ext.attn_decode_grouped_qs(B * H, G, torch.cuda.get_device_properties(0).multi_processor_count)
+    return {"kernel": "attn_decode_grouped", "R": R, "G": G, "H": H, "D": D, "prefix": prefix, "suffix": suffix,
+            "qs": qs, "kv_bytes": nbytes, "kv_bytes_rows": nbytes_rows, "cache_sets": nsets, **out}
+
+
+def grouped_model_step(R, G, prefix, suffix, reps):
+    """One whole ``decode_step(decode_linears="rows")`` of GPT-2 small per cache kind: R rows over a plain cache
+    that holds prefix + suffix keys each, and over a ``GroupKVCache`` of R / G prompts."""
+    from distributed_pipeline_amd.models import build_model
+    torch.manual_seed(0)
+    model = build_model(model="gpt2", config_name="gpt2", precision="bf16", seq_len=1024, dropout=0.0).cuda().eval()
+    for p in model.parameters():
+        p._dpa_shadow = p.detach().to(torch.bfloat16)
+    tok = torch.randint(0, model.cfg["vocab_size"], (R,), device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
+    plain, group = model.init_cache(R, 1024), model.init_group_cache(R // G, G, prefix, 1024 - prefix)
+    for buf in (plain.buf, group.prefix.buf, group.suffix.buf):
+        buf.normal_()
+
+    def step_plain():
+        plain.lens.fill_(prefix + suffix)  # the same position every call
+        return model.decode_step(tok, plain, decode_linears="rows")
+
+    def step_group():
+        group.prefix.lens.fill_(prefix)
+        group.suffix.lens.fill_(suffix)
+        return model.decode_step(tok, group, decode_linears="rows")
+
+    out = interleaved({"plain_cache": (step_plain, 20), "group_cache": (step_group, 20)}, reps, warmup=2)
+    out["group_cache"]["time_vs_plain"] = round(out["group_cache"]["median_ms"] / out["plain_cache"]["median_ms"], 3)
+    return {"model": "gpt2", "decode_linears": "rows", "R": R, "G": G, "prefix": prefix, "suffix": suffix, **out}
+
+
 def model_step(B, n, reps):
     from distributed_pipeline_amd.models import build_model
     torch.manual_seed(0)
@@ -219,6 +295,10 @@ def main():
     ap.add_argument("--extend", action="store_true",
                     help="the rows of the cache-extending kernel instead: B in 1,8,64 x (len, T) in --extend_shapes")
     ap.add_argument("--extend_shapes", default="0:128,512:32,896:128")
+    ap.add_argument("--grouped", action="store_true",
+                    help="the cells of the grouped decode kernel instead: B*G in --B x G in 2..32 x prefix x suffix")
+    ap.add_argument("--prefixes", default="128,512,896")
+    ap.add_argument("--suffixes", default="1,64")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a HIP device"
@@ -228,6 +308,17 @@ def main():
             for n, T in (tuple(int(x) for x in sh.split(":")) for sh in a.extend_shapes.split(",")):
                 lines.append(json.dumps(extend_shape(B, a.H, a.D, a.Lmax, n, T, a.reps, a.spread_mb << 20)))
                 print(lines[-1], flush=True)
+        a.B, a.no_model = "", True
+    if a.grouped:
+        for R in (int(x) for x in a.B.split(",")):
+            for G in (g for g in (2, 4, 8, 16, 32) if g <= R):
+                for pfx in (int(x) for x in a.prefixes.split(",")):
+                    for sfx in (int(x) for x in a.suffixes.split(",")):
+                        lines.append(json.dumps(grouped_shape(R, G, a.H, a.D, pfx, sfx, a.reps, a.spread_mb << 20)))
+                        print(lines[-1], flush=True)
+        if not a.no_model:
+            lines.append(json.dumps(grouped_model_step(64, 8, 512, 16, a.reps)))
+            print(lines[-1], flush=True)
         a.B, a.no_model = "", True
     for B in (int(x) for x in a.B.split(",") if x):
         for n in (int(x) for x in a.lens.split(",")):
