@@ -369,7 +369,53 @@ static c10::optional<at::Tensor> linear_rows(const at::Tensor& x, const at::Tens
   return y;
 }
 
+// The same Linear on one-byte weights (csrc/linear_rows_fp8.hip): x [M, K] bf16, codes [N, K] uint8 (e4m3fn,
+// row-major, a row slice of a larger matrix works), exps [N] int8 (one per weight row, kv8_quantize's format), bias
+// [N] bf16 or None -> y [M, N] bf16 = act(ldexp(x float(codes)^T, exps) + b), or None for a case the kernel does
+// not cover (CPU, dtype of x, M > 128, K % 64, row layout).  `out` as in linear_rows.
+static c10::optional<at::Tensor> linear_rows_fp8(const at::Tensor& x, const at::Tensor& codes, const at::Tensor& exps,
+                                                 c10::optional<at::Tensor> bias, int64_t act,
+                                                 c10::optional<at::Tensor> out) {
+  TORCH_CHECK(x.dim() == 2 && codes.dim() == 2 && exps.dim() == 1, "linear_rows_fp8: x [M, K], codes [N, K], exps [N]");
+  const int64_t M = x.size(0), K = x.size(1), N = codes.size(0);
+  TORCH_CHECK(codes.size(1) == K, "linear_rows_fp8: x [M, ", K, "] and codes [N, ", codes.size(1), "] do not agree");
+  TORCH_CHECK(N >= 1 && exps.size(0) == N, "linear_rows_fp8: codes must have N >= 1 rows and exps N entries");
+  TORCH_CHECK(act >= 0 && act <= 3, "linear_rows_fp8: act must be 0 (none), 1 (gelu), 2 (tanh) or 3 (silu)");
+  TORCH_CHECK(codes.scalar_type() == at::kByte && exps.scalar_type() == at::kChar,
+              "linear_rows_fp8: codes must be uint8 and exps int8");
+  if (has(bias)) {
+    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == N, "linear_rows_fp8: bias must be [N]");
+    TORCH_CHECK(bias->scalar_type() == x.scalar_type(), "linear_rows_fp8: x and bias must have one dtype");
+  }
+  if (has(out))
+    TORCH_CHECK(out->dim() == 2 && out->size(0) == M && out->size(1) == N && out->scalar_type() == x.scalar_type(),
+                "linear_rows_fp8: out must be [M, N] in x's dtype");
+  if (!x.is_cuda() || !codes.is_cuda() || codes.device() != x.device()) return c10::nullopt;
+  if (!exps.is_cuda() || exps.device() != x.device() || !exps.is_contiguous()) return c10::nullopt;
+  if (has(bias) && (!bias->is_cuda() || bias->device() != x.device() || !bias->is_contiguous())) return c10::nullopt;
+  if (has(out) && (!out->is_cuda() || out->device() != x.device())) return c10::nullopt;
+  if (x.scalar_type() != at::kBFloat16 || M < 1 || M > 128 || K < 64 || K % 64) return c10::nullopt;
+  auto rows_ok = [&](const at::Tensor& t, int64_t unit) {  // last stride 1, 16-byte row starts, rows that do not overlap
+    return t.stride(1) == 1 && (t.size(0) == 1 || (t.stride(0) % unit == 0 && t.stride(0) >= t.size(1))) &&
+           reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+  };
+  if (!rows_ok(x, 8) || !rows_ok(codes, 16)) return c10::nullopt;
+  if (has(out) && ((N > 1 && out->stride(1) != 1) || (M > 1 && out->stride(0) < N))) return c10::nullopt;
+  const c10::DeviceGuard guard(x.device());
+  at::Tensor y = has(out) ? *out : at::empty({M, N}, x.options());
+  const bool ok = dpa::launch_linear_rows_fp8(bf_ptr(x), M > 1 ? x.stride(0) : K, codes.data_ptr<uint8_t>(),
+                                              N > 1 ? codes.stride(0) : K, exps.data_ptr<int8_t>(), opt_bf_ptr(bias),
+                                              bf_mut(y), M > 1 ? y.stride(0) : N, (int)M, N, (int)K, (int)act,
+                                              cur_stream());
+  if (!ok) return c10::nullopt;
+  return y;
+}
+
 void dpa::register_attention(pybind11::module& m) {
+  m.def("linear_rows_fp8", &linear_rows_fp8,
+        "a decode step's Linear on one-byte weights: x [M <= 128, K % 64 == 0] bf16 against e4m3fn codes [N, K] uint8 with one int8 exponent per row (+ bias [N], act code) -> y [M, N] bf16, each output row a function of its input row alone | None (case not covered)",
+        py::arg("x"), py::arg("codes"), py::arg("exps"), py::arg("bias") = py::none(), py::arg("act") = 0,
+        py::arg("out") = py::none());
   m.def("linear_rows", &linear_rows,
         "a decode step's Linear: x [M <= 128, K % 64 == 0] bf16 against weight [N, K] bf16 (+ bias [N], act code) -> y [M, N] bf16, each output row a function of its input row alone | None (case not covered)",
         py::arg("x"), py::arg("weight"), py::arg("bias") = py::none(), py::arg("act") = 0, py::arg("out") = py::none());

@@ -313,6 +313,19 @@ int attn_decode_grouped_qs(int64_t BH, int G, int ncu);
 bool launch_linear_rows(const uint16_t* x, int64_t ldx, const uint16_t* W, int64_t ldw, const uint16_t* bias,
                         uint16_t* y, int64_t ldy, int M, int64_t N, int K, int act, hipStream_t s);
 
+// ---- linear_rows_fp8.hip: the same Linears on one-byte weights, W8A16 (K-M29) ----
+// y[m][n] = bf16(act(ldexp(sum_k x[m][k] float(W8[n][k]), we[n]) + bias[n])): x [M][K] and y [M][N] bf16 with rows
+// ldx and ldy elements apart, W8 [N][K] e4m3fn codes with rows ldw bytes apart, we [N] int8 exponents (the format
+// of launch_kv8_quantize, one per weight row), bias [N] bf16 or null, act a code of act.h; fp32 products and sums,
+// the exponent applied once per output as an exact scaling, fp32 bias add and act, one rounding.  The bits of
+// y[m][n] depend on x[m][:], W8[n][:], we[n], bias[n], act, K and N alone.  One launch, no workspace, no atomics.
+// Rows m >= M and weight rows n >= N are neither loaded nor stored, we included.  false, with no launch: M outside
+// 1 .. 128, N < 1, K no positive multiple of 64, ldx < K, ldw < K, ldy < N, ldx no multiple of 8, ldw no multiple
+// of 16, x or W8 not 16-byte aligned, an unknown act or a null pointer.
+bool launch_linear_rows_fp8(const uint16_t* x, int64_t ldx, const uint8_t* W8, int64_t ldw, const int8_t* we,
+                            const uint16_t* bias, uint16_t* y, int64_t ldy, int M, int64_t N, int K, int act,
+                            hipStream_t s);
+
 // ---- beam_step.hip: log-softmax + score + top-W of W V candidates (beam search) ----------
 // logits [B][W][V] fp32 or bf16 (element strides stride_b, stride_w >= 0 - 0 repeats a row - and 1),
 // scores fp32 [B][W], finished bytes [B][W] -> the first W candidates of each b in the order

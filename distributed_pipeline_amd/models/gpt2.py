@@ -94,23 +94,57 @@ class GPT2LMModel(nn.Module):
                        device, dtype, kv_dtype=kv_dtype)
 
     def _rows(self, decode_linears, n_rows, ref):
-        """Whether a call of ``n_rows`` rows on ``ref``'s device runs its Linears through
-        ``ops.decode.linear_rows``: asked for, at most 128 rows, bf16 compute on a HIP device."""
-        if decode_linears not in ("tile", "rows"):
-            raise ValueError(f"decode_linears must be 'tile' or 'rows', got {decode_linears!r}")
+        """How a call of ``n_rows`` rows on ``ref``'s device runs its Linears: "rows" (through
+        ``ops.decode.linear_rows``: asked for, at most 128 rows, bf16 compute on a HIP device), "rows_fp8"
+        (through ``ops.decode.linear_rows_fp8`` on the quantized snapshot: wherever it is asked for) or False
+        (``ops.linear``)."""
+        if decode_linears not in ("tile", "rows", "rows_fp8"):
+            raise ValueError(f"decode_linears must be 'tile', 'rows' or 'rows_fp8', got {decode_linears!r}")
+        if decode_linears == "rows_fp8":
+            return "rows_fp8"
         from ..ops.decode import ROWS_MAX_M
         return (decode_linears == "rows" and n_rows <= ROWS_MAX_M and ref.is_cuda
-                and self.compute_dtype == torch.bfloat16)
+                and self.compute_dtype == torch.bfloat16) and "rows"
 
-    def _lin_rows(self, lin, t):
-        """``lin(t)`` for a ``layers.Linear`` through ``ops.decode.linear_rows`` on the bf16 shadows."""
-        from ..ops.decode import linear_rows
+    @torch.no_grad()
+    def quantize_decode_weights(self):
+        """Build (or rebuild) the one-byte snapshot that ``decode_linears="rows_fp8"`` computes with: for the
+        weight of every block's qkv, attn_proj, mlp_fc and mlp_proj and for the tied ``wte``,
+        ``ops.decode.kv_quantize_ref`` of the compute-dtype values - e4m3fn codes uint8 [N, K] and one int8
+        power-of-two exponent per weight row.  A one-time PyTorch op.  The snapshot is kept on the module,
+        is not part of ``state_dict`` and does NOT follow later weight updates (an optimizer step, a loaded
+        checkpoint, a move to another device): call this again after one.  The ``rows_fp8`` paths build it on
+        first use if it is absent.  Biases, LayerNorms and the embedding lookup are not quantized."""
+        from ..ops.decode import kv_quantize_ref
         dt = self.compute_dtype
-        y = linear_rows(t.reshape(-1, t.shape[-1]), ops.shadow(lin.weight, dt), ops.shadow(lin.bias, dt), act=lin.act)
+        weights = [self.wte.weight] + [lin.weight for blk in self.h
+                                       for lin in (blk.attn.qkv, blk.attn_proj, blk.mlp_fc, blk.mlp_proj)]
+        self._decode_w8 = {id(w): kv_quantize_ref(ops.shadow(w, dt)) for w in weights}
+        return self
+
+    def _w8(self, weight):
+        """(codes, exponents) of ``weight`` from the snapshot, built on first use."""
+        if getattr(self, "_decode_w8", None) is None:
+            self.quantize_decode_weights()
+        return self._decode_w8[id(weight)]
+
+    def _lin_rows(self, lin, t, rows="rows"):
+        """``lin(t)`` for a ``layers.Linear`` through ``ops.decode.linear_rows`` on the bf16 shadows, or with
+        ``rows="rows_fp8"`` through ``ops.decode.linear_rows_fp8`` on the snapshot (the bias stays as it is)."""
+        from ..ops.decode import linear_rows, linear_rows_fp8
+        dt = self.compute_dtype
+        t2 = t.reshape(-1, t.shape[-1])
+        if rows == "rows_fp8":
+            y = linear_rows_fp8(t2, *self._w8(lin.weight), ops.shadow(lin.bias, dt), act=lin.act)
+        else:
+            y = linear_rows(t2, ops.shadow(lin.weight, dt), ops.shadow(lin.bias, dt), act=lin.act)
         return y.view(*t.shape[:-1], -1)
 
     def _head(self, a, rows):
         """The tied head on ``a`` [R, H] -> logits [R, V]."""
+        if rows == "rows_fp8":
+            from ..ops.decode import linear_rows_fp8
+            return linear_rows_fp8(a, *self._w8(self.wte.weight))
         if rows:
             from ..ops.decode import linear_rows
             return linear_rows(a, ops.shadow(self.wte.weight, self.compute_dtype))
@@ -119,16 +153,17 @@ class GPT2LMModel(nn.Module):
     def _blocks(self, x, a, attend, rows=False):
         """The block stack of ``hidden_states`` in eval mode with ``attend(i, qkv)`` as layer i's
         attention over its packed projection -> ln_f of the last residual stream.  ``rows``: the four
-        Linears of every block run through ``ops.decode.linear_rows`` (:meth:`_rows` says when)."""
+        Linears of every block run through ``ops.decode.linear_rows`` or, for "rows_fp8",
+        ``ops.decode.linear_rows_fp8`` (:meth:`_rows` says which)."""
         lns = [blk.ln_1 for blk in self.h] + [self.ln_f]
         for i, blk in enumerate(self.h):
             if rows:
-                h = self._lin_rows(blk.attn_proj, attend(i, self._lin_rows(blk.attn.qkv, a)))
+                h = self._lin_rows(blk.attn_proj, attend(i, self._lin_rows(blk.attn.qkv, a, rows)), rows)
             else:
                 h = blk.attn_proj(attend(i, blk.attn.qkv(a)))
             x, a = ops.residual_layernorm(h, x, blk.ln_2.weight, blk.ln_2.bias, 0.0, blk.ln_2.eps, False)
             if rows:
-                h = self._lin_rows(blk.mlp_proj, self._lin_rows(blk.mlp_fc, a))
+                h = self._lin_rows(blk.mlp_proj, self._lin_rows(blk.mlp_fc, a, rows), rows)
             else:
                 h = ops.mlp(a, blk.mlp_fc, blk.mlp_proj)
             x, a = ops.residual_layernorm(h, x, lns[i + 1].weight, lns[i + 1].bias, 0.0, lns[i + 1].eps, False)
@@ -141,7 +176,8 @@ class GPT2LMModel(nn.Module):
         prompt positions copied into ``cache`` (quantized into an fp8 cache; the prompt's own forward
         attends over the unquantized values), ``cache.lens = lens`` -> the logits [B, V] at each row's
         last prompt position.  ``decode_linears="rows"``: the head on those B rows runs through
-        ``ops.decode.linear_rows`` (see :meth:`decode_step`); the prompt's forward is unchanged.
+        ``ops.decode.linear_rows`` (see :meth:`decode_step`), with "rows_fp8" through
+        ``ops.decode.linear_rows_fp8``; the prompt's forward is unchanged and keeps its unquantized weights.
 
         ``chunk = C >= 1``: the prompt goes through :meth:`extend` in pieces of C columns instead,
         starting from an empty cache - piece ``p0`` with ``counts = clamp(lens - p0, 0, C)``, so nothing is
@@ -252,8 +288,12 @@ class GPT2LMModel(nn.Module):
         padded into the training GEMM's tiles.  "rows" runs qkv, attn_proj, mlp_fc with its GELU,
         mlp_proj and the tied head through ``ops.decode.linear_rows`` on the bf16 shadows - one launch
         each, an output row a function of its input row alone - where the call has at most 128 rows and
-        computes in bf16 on a HIP device; anywhere else it is "tile".  The residual adds, the
-        LayerNorms and the attention are the same in both.  The two modes round differently."""
+        computes in bf16 on a HIP device; anywhere else it is "tile".  "rows_fp8" runs the same five through
+        ``ops.decode.linear_rows_fp8`` on the one-byte snapshot of :meth:`quantize_decode_weights` (built on
+        first use; it does not follow later weight updates) - on any device and at any row count, the op's
+        PyTorch definition serving what its kernel does not, so the mode means the same numbers everywhere.
+        The embedding lookup reads ``wte`` unquantized and the biases stay as they are.  The residual adds,
+        the LayerNorms and the attention are the same in all three.  The modes round differently."""
         from ..ops.decode import attention_decode, attention_decode_fp8
         if isinstance(cache, GroupKVCache):
             if table is not None:
@@ -303,7 +343,7 @@ class GPT2LMModel(nn.Module):
         ``cache``: one from :meth:`init_cache` to use (default: a new one of just the size needed).
         ``kv_dtype``: "bf16" or "fp8" - the one-byte cache, half the bytes per cached token - for
         the new cache (default "bf16"); given together with a ``cache`` of the other kind it is an
-        error.  ``decode_linears``: "tile" or "rows", handed to :meth:`prefill` and every
+        error.  ``decode_linears``: "tile", "rows" or "rows_fp8", handed to :meth:`prefill` and every
         :meth:`decode_step`.  ``prefill_chunk``: :meth:`prefill`'s ``chunk`` (0: the single forward).
         The loop runs on the device; the host looks at it once every ``check_every`` steps (0:
         never), to stop early when every row has finished.
@@ -620,7 +660,7 @@ class GPT2LMModel(nn.Module):
         max_draft) -> (draft [B, max_draft], k [B])`` to use instead - ``history[b, :n[b]]`` is the
         row's prompt and output so far.  ``return_stats`` adds a dict: ``model_calls`` (iterations with
         a live row), ``proposed`` and ``accepted`` guesses, read back once at the end.
-        ``decode_linears``: "tile" or "rows", handed to :meth:`prefill` and every :meth:`decode_block`.
+        ``decode_linears``: "tile", "rows" or "rows_fp8", handed to :meth:`prefill` and every :meth:`decode_block`.
 
         The logit processors of :meth:`generate` are not available here: the guesses continue
         repeated n-grams, which is what those penalties forbid, and the queries of a block would
@@ -741,7 +781,7 @@ class GPT2LMModel(nn.Module):
         logits are one row per prompt repeated for every beam, so they are penalised once, before
         they are expanded.  The scores are sums of the log-softmax of the processed logits.
 
-        ``decode_linears``: "tile" or "rows", handed to :meth:`prefill` and every :meth:`decode_step`
+        ``decode_linears``: "tile", "rows" or "rows_fp8", handed to :meth:`prefill` and every :meth:`decode_step`
         (``B W`` rows)."""
         from ..ops.decode import beam_step, penalize_logits_
         penalties, min_new = _logit_processors(repetition_penalty, presence_penalty, frequency_penalty,

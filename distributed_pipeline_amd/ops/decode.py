@@ -4,7 +4,7 @@ the indirection table of a beam search), the same for a block of new tokens with
 fill it (lookahead decoding), one beam-search step, the choice of the next token, the logit
 processors in front of it (repetition, presence and frequency penalty, no-repeat-n-gram ban), the
 statistics of a logits row against a given token (teacher-forced scoring), and the Linears of a
-decode step, whose few rows stand against whole weight matrices.
+decode step, whose few rows stand against whole weight matrices - in bf16 or as one-byte codes.
 
 Attention of one decode step
 ----------------------------
@@ -318,6 +318,30 @@ K, such as a row slice of a larger matrix, is served); ``bias`` bf16 or absent: 
 csrc/linear_rows.hip.  Anything else (CPU, fp32, a larger M, another K): :func:`linear_rows_ref`, the
 definition in fp32 PyTorch (its GELU is the exact one; the kernel's is ``gelu_f``, below bf16 resolution
 of it).
+
+The same Linears on one-byte weights: ``linear_rows_fp8``
+---------------------------------------------------------
+``linear_rows_fp8(x [M, K], codes uint8 [N, K], exp int8 [N], bias [N] | None = None, *, act="none") -> y [M, N]``
+in ``x``'s dtype (W8A16: the weight is one byte per element, ``x`` is not quantized):
+
+* The weight is ``kv_quantize``'s format applied per weight row (per output feature): ``codes, exp =
+  kv_quantize_ref(weight)``, once, off the hot path; ``W^[n, k] = float(codes[n, k]) * 2^exp[n]``.
+* ``y[m, n] = round_to_dtype(act(ldexp(sum_k x[m, k] * float(codes[n, k]), exp[n]) + b[n]))``: products and the
+  sum in fp32, the row's exponent applied once to the finished sum (a power of two: exact), bias and ``act``
+  in fp32, one rounding.  In exact arithmetic this is ``linear_rows(x, W^, b)``.
+* Inference only: no autograd.  ``M == 0`` returns an empty tensor.
+
+The row contract is ``linear_rows``'s: on the kernel path the bits of ``y[m, n]`` are a function of ``x[m, :]``,
+``codes[n, :]``, ``exp[n]``, ``b[n]``, ``act``, K and N - not of M, of where the row stands, of the other rows or
+of the launch geometry.  K is split among the four waves of a workgroup by K alone, never across workgroups;
+no atomics.  The bits need not equal ``linear_rows`` on ``W^``: the k grouping differs.
+
+bf16 ``x`` on a HIP device with last stride 1 and 16-byte aligned rows, ``1 <= M <= 128``, K a multiple of 64,
+any ``N >= 1``; ``codes`` with last stride 1, a 16-byte aligned base and a row stride that is a multiple of 16
+bytes (a row slice of a larger matrix is served); ``bias`` bf16 or absent: one launch of
+csrc/linear_rows_fp8.hip, which reads every code once, converts in registers (``v_cvt_pk_f32_fp8``; every e4m3fn
+value is exactly a bf16 value) and feeds the bf16 MFMA.  Anything else (CPU, fp32, a larger M, another K):
+:func:`linear_rows_fp8_ref`, ``F.linear(x.float(), kv_dequantize(codes, exp), b)`` and ``act`` in fp32 PyTorch.
 """
 import math
 import struct
@@ -1165,3 +1189,48 @@ def linear_rows(x, weight, bias=None, *, act="none"):
             if out is not None:
                 return out
     return linear_rows_ref(x, weight, bias, act=act)
+
+
+# ---- linear_rows_fp8 ----------------------------------------------------------------------------
+
+
+def _check_linear_rows_fp8(x, codes, exp, bias, act):
+    if act not in _ROWS_ACTS:
+        raise ValueError(f"act must be one of {sorted(_ROWS_ACTS)}, got {act!r}")
+    if x.dim() != 2 or codes.dim() != 2 or codes.shape[1] != x.shape[1] or codes.shape[0] < 1:
+        raise ValueError(f"x must be [M, K] and codes [N >= 1, K], got {tuple(x.shape)}, {tuple(codes.shape)}")
+    if tuple(exp.shape) != (codes.shape[0],):
+        raise ValueError(f"exp must be [{codes.shape[0]}], got {tuple(exp.shape)}")
+    if codes.dtype != torch.uint8 or exp.dtype != torch.int8:
+        raise ValueError(f"codes must be uint8 and exp int8, got {codes.dtype}, {exp.dtype}")
+    if not x.is_floating_point():
+        raise ValueError(f"x must be a float tensor, got {x.dtype}")
+    if bias is not None and tuple(bias.shape) != (codes.shape[0],):
+        raise ValueError(f"bias must be [{codes.shape[0]}], got {tuple(bias.shape)}")
+
+
+def linear_rows_fp8_ref(x, codes, exp, bias=None, *, act="none"):
+    """The definition in fp32 PyTorch (any device, any float dtype of ``x``) -> y [M, N] in ``x``'s dtype."""
+    _check_linear_rows_fp8(x, codes, exp, bias, act)
+    z = F.linear(x.detach().float(), kv_dequantize(codes, exp), None if bias is None else bias.detach().float())
+    z = {"none": lambda t: t, "gelu": F.gelu, "tanh": torch.tanh, "silu": F.silu}[act](z)
+    return z.to(x.dtype)
+
+
+@torch.no_grad()
+def linear_rows_fp8(x, codes, exp, bias=None, *, act="none"):
+    """-> y [M, N] = act(x W^^T + b) in ``x``'s dtype for the one-byte weight ``W^ = float(codes) * 2^exp`` (one
+    exponent per weight row): the module docstring has the definition and the row contract."""
+    _check_linear_rows_fp8(x, codes, exp, bias, act)
+    if x.shape[0] == 0:
+        return x.new_empty(0, codes.shape[0])
+    if x.is_cuda:
+        ext = get_ext()  # raises on a GPU without the built extension: no quiet fall-back
+        if ext is not None and x.dtype == torch.bfloat16 and (bias is None or bias.dtype == x.dtype):
+            if x.stride(-1) != 1 or x.stride(0) % 8 or x.data_ptr() % 16:
+                x = x.contiguous()
+            out = ext.linear_rows_fp8(x, codes, exp.contiguous(), None if bias is None else bias.contiguous(),
+                                      _ROWS_ACTS[act])
+            if out is not None:
+                return out
+    return linear_rows_fp8_ref(x, codes, exp, bias, act=act)

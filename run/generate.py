@@ -62,6 +62,12 @@ tied head - through ``ops.decode.linear_rows``, a kernel that streams each weigh
 rows, instead of padding the rows into the training GEMM's tiles (``tile``, the default).  It applies where
 a step has at most 128 rows (``--batch_size`` times ``--num_beams`` or ``--lookahead``) in bf16 on a GPU and
 combines with every other flag.  The two modes round differently, so continuations can differ.
+
+``--decode_linears rows_fp8`` runs the same Linears on one-byte weights: after the checkpoint is loaded every
+such weight and the tied ``wte`` are quantized once to e4m3fn codes with one power-of-two exponent per weight row
+(``--kv_dtype fp8``'s format) and the steps run ``ops.decode.linear_rows_fp8``, which reads half the bytes.  The
+embedding lookup, the biases and the prompt's own forward keep the bf16 weights.  The mode means the same numbers
+on any device and at any row count: where the kernel does not apply, its PyTorch definition runs.
 """
 import json
 import os

@@ -1,7 +1,9 @@
 """Time the Linears of one GPT-2 decode step: the row kernel (csrc/linear_rows.hip through
 ``ext.linear_rows``) against today's ``ops.nn.linear`` on the same tensors (the rows padded into the
 training GEMM's tiles; hipBLASLt for the head) and against a device copy of the weight's bytes - the
-bandwidth yardstick - all in one process and interleaved.
+bandwidth yardstick - all in one process and interleaved.  Beside them the same Linear on one-byte weights
+(csrc/linear_rows_fp8.hip through ``ext.linear_rows_fp8``, the weights quantized with ``kv_quantize_ref``) and a
+device copy of the fp8 weight's bytes, on weight copies of their own spread over the same number of bytes.
 
     python tools/decode_linear_bench.py [--M 1,8,64,128] [--reps 7] [--spread_mb 768] [--no_model] [--out FILE]
 
@@ -11,7 +13,7 @@ different copies of the weight, so that ``spread_mb`` of reads pass before one r
 served from the last-level cache.
 
 It also times one whole ``GPT2LMModel.decode_step`` at (B, len) = (64, 512) and (8, 512) with
-``decode_linears="tile"`` and ``"rows"``, interleaved in the same run (``--no_model`` skips it).
+``decode_linears="tile"``, ``"rows"`` and ``"rows_fp8"``, interleaved in the same run (``--no_model`` skips it).
 
 Every variant of a shape is timed in turn inside each repetition; a repetition is ``inner`` back-to-back
 calls between two device events; medians and min-max over the repetitions.
@@ -35,6 +37,7 @@ ACT_CODES = {"none": 0, "gelu": 1}
 def shape(name, N, K, act, has_bias, M, reps, spread_bytes):
     from distributed_pipeline_amd.ops import nn
     from distributed_pipeline_amd.ops._ext import get_ext
+    from distributed_pipeline_amd.ops.decode import kv_quantize_ref
     ext = get_ext(required=True)
     g = torch.Generator(device="cuda").manual_seed(0)
     nbytes = N * K * 2
@@ -42,13 +45,28 @@ def shape(name, N, K, act, has_bias, M, reps, spread_bytes):
     ws = [torch.empty(N, K, device="cuda", dtype=torch.bfloat16).normal_(0.0, K ** -0.5, generator=g)
           for _ in range(nsets)]
     dst = [torch.empty_like(ws[0]) for _ in range(min(nsets, 8))]
+    # the one-byte weights: twice as many copies, so that as many bytes pass before one repeats
+    nsets8 = 2 * nsets
+    q = [kv_quantize_ref(w) for w in ws]
+    w8 = [q[i % nsets][0].clone() for i in range(nsets8)]
+    e8 = [q[i % nsets][1] for i in range(nsets8)]
+    del q
+    dst8 = [torch.empty_like(w8[0]) for _ in range(min(nsets8, 8))]
     x = torch.randn(M, K, device="cuda", generator=g).bfloat16()
     b = torch.randn(N, device="cuda", generator=g).bfloat16() if has_bias else None
-    turn = {"rows": 0, "tile": 0, "copy": 0}
+    turn = {"rows": 0, "tile": 0, "copy": 0, "rows_fp8": 0, "copy_fp8": 0}
 
-    def nxt(key):
-        turn[key] = (turn[key] + 1) % nsets
+    def nxt(key, n=nsets):
+        turn[key] = (turn[key] + 1) % n
         return turn[key]
+
+    def rows_fp8():
+        i = nxt("rows_fp8", nsets8)
+        return ext.linear_rows_fp8(x, w8[i], e8[i], b, ACT_CODES[act])
+
+    def copy_fp8():
+        i = nxt("copy_fp8", nsets8)
+        return dst8[i % len(dst8)].copy_(w8[i])
 
     def rows():
         return ext.linear_rows(x, ws[nxt("rows")], b, ACT_CODES[act])
@@ -61,10 +79,14 @@ def shape(name, N, K, act, has_bias, M, reps, spread_bytes):
         i = nxt("copy")
         return dst[i % len(dst)].copy_(ws[i])
 
-    assert rows() is not None, "the row kernel must take this shape"
-    out = interleaved({"rows": (rows, 500), "tile": (tile, 200), "copy": (copy, 500)}, reps)
+    assert rows() is not None and rows_fp8() is not None, "the row kernels must take this shape"
+    out = interleaved({"rows": (rows, 500), "rows_fp8": (rows_fp8, 500), "tile": (tile, 200), "copy": (copy, 500),
+                       "copy_fp8": (copy_fp8, 500)}, reps)
     for key in out:
-        out[key]["GBps"] = round(nbytes / out[key]["median_ms"] / 1e6, 1)
+        out[key]["GBps"] = round((nbytes // 2 if key.endswith("fp8") else nbytes) / out[key]["median_ms"] / 1e6, 1)
+    out["rows_fp8"]["fraction_of_fp8_copy_rate"] = round(out["copy_fp8"]["median_ms"] / out["rows_fp8"]["median_ms"], 3)
+    out["rows_fp8"]["speedup_vs_rows"] = round(out["rows"]["median_ms"] / out["rows_fp8"]["median_ms"], 2)
+    out["rows_fp8"]["ranges_apart_from_rows"] = bool(out["rows_fp8"]["max_ms"] < out["rows"]["min_ms"])
     # the copy's rate counts each byte once, though it reads and writes it
     out["rows"]["fraction_of_copy_rate"] = round(out["copy"]["median_ms"] / out["rows"]["median_ms"], 3)
     out["rows"]["speedup_vs_tile"] = round(out["tile"]["median_ms"] / out["rows"]["median_ms"], 2)
@@ -95,8 +117,10 @@ def model_steps(shapes, reps):
             model.prefill(ids[:1, :n - 1], torch.full((1,), n - 1, dtype=torch.int32, device="cuda"), one)
         alone = model.decode_step(ids[:1, n - 1], one, decode_linears="rows")
         same = bool(torch.equal(alone.view(torch.int16), step("rows")[:1].view(torch.int16)))
-        out = interleaved({"tile": (lambda: step("tile"), 20), "rows": (lambda: step("rows"), 20)}, reps, warmup=2)
+        out = interleaved({"tile": (lambda: step("tile"), 20), "rows": (lambda: step("rows"), 20),
+                           "rows_fp8": (lambda: step("rows_fp8"), 20)}, reps, warmup=2)
         out["rows"]["speedup_vs_tile"] = round(out["tile"]["median_ms"] / out["rows"]["median_ms"], 2)
+        out["rows_fp8"]["speedup_vs_rows"] = round(out["rows"]["median_ms"] / out["rows_fp8"]["median_ms"], 2)
         res.append({"model": "gpt2", "B": B, "len": n, "row_0_alone_bit_equal_rows_mode": same, **out})
     return res
 
