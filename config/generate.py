@@ -81,15 +81,17 @@ class ContinueSettings(S):
         = _("bf16", "Storage of the K/V cache. fp8: one byte per element (OCP e4m3fn codes and one power-of-two "
                     "exponent per cached row), half the memory and half the bytes a decode step reads; the "
                     "continuations can differ from bf16's. Excludes --num_beams > 1 and --lookahead.")
-    decode_linears: Choice("tile", "rows", "rows_fp8") \
+    decode_linears: Choice("tile", "rows", "rows_fp8", "rows_fused") \
         = _("tile", "How the Linears of the decode steps run. tile: through the training GEMM, the rows padded into "
                     "its tiles. rows: through the weight-streaming row kernel (ops.decode.linear_rows), one launch "
                     "per Linear and the tied head included, where a step has at most 128 rows; an output row is "
                     "then a function of its input row alone. rows_fp8: the same Linears on one-byte weights - "
                     "e4m3fn codes and one power-of-two exponent per weight row, quantized once after loading "
                     "(ops.decode.linear_rows_fp8) - half the weight bytes a step reads, on any device and at any "
-                    "row count. The modes round differently, and rows_fp8 changes the weights, so continuations "
-                    "can differ.")
+                    "row count. rows_fused: rows with each block's two LayerNorms and two residual adds inside the "
+                    "row kernel (its ln and residual keywords) - five launches per block instead of seven, under "
+                    "rows' conditions. The modes round differently, and rows_fp8 changes the weights, so "
+                    "continuations can differ.")
     prefill_chunk: int \
         = _(0, "Run the prompts through the cache-extending attention kernel (ops.decode.attention_extend) in "
                "pieces of this many tokens instead of one causal forward over the padded prompt matrix; 0 = off. "
@@ -146,8 +148,8 @@ class GenerateSettings(
             raise ValueError(f"--noise must be torch or philox, got {self.noise!r}")
         if self.kv_dtype not in ("bf16", "fp8"):
             raise ValueError(f"--kv_dtype must be bf16 or fp8, got {self.kv_dtype!r}")
-        if self.decode_linears not in ("tile", "rows", "rows_fp8"):
-            raise ValueError(f"--decode_linears must be tile, rows or rows_fp8, got {self.decode_linears!r}")
+        if self.decode_linears not in ("tile", "rows", "rows_fp8", "rows_fused"):
+            raise ValueError(f"--decode_linears must be tile, rows, rows_fp8 or rows_fused, got {self.decode_linears!r}")
         if self.kv_dtype == "fp8" and (self.num_beams > 1 or self.lookahead > 0):
             raise ValueError("--kv_dtype fp8 is served by generate's own loop: the table (--num_beams > 1) and "
                              "block (--lookahead) decode kernels have no fp8 variant")

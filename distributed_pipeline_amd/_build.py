@@ -31,11 +31,11 @@ COMMON = ["-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-D__HIP_PLATFORM_AMD
           "-Wno-unused-result", "-Wno-unused-command-line-argument"]  # every TU, before its -O flags
 # Flags of single kernel TUs.  linear_rows.hip is built without the packed-fp32 VALU forms (v_pk_add_f32,
 # v_pk_mul_f32, v_pk_fma_f32): its row contract is a bit-for-bit one and its epilogue needs none of them;
-# linear_rows_fp8.hip has the same contract.
+# linear_rows_fp8.hip and linear_rows_fused.hip have the same contract.
 # attn_extend.hip and attn_decode_grouped.hip likewise: their rescale of O is a per-lane scalar factor.
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-TU_FLAGS = {"linear_rows.hip": _NO_PK_F32, "linear_rows_fp8.hip": _NO_PK_F32, "attn_extend.hip": _NO_PK_F32,
-            "attn_decode_grouped.hip": _NO_PK_F32}
+TU_FLAGS = {"linear_rows.hip": _NO_PK_F32, "linear_rows_fp8.hip": _NO_PK_F32, "linear_rows_fused.hip": _NO_PK_F32,
+            "attn_extend.hip": _NO_PK_F32, "attn_decode_grouped.hip": _NO_PK_F32}
 
 
 def _hipcc():

@@ -334,9 +334,15 @@ static c10::optional<std::vector<at::Tensor>> kv8_quantize(const at::Tensor& x) 
 // larger matrix works), bias [N] bf16 or None, act a code of act.h -> y [M, N] bf16 = act(x W^T + b), or None
 // for a case the kernel does not cover (CPU, dtype, M > 128, K % 64, row layout): the caller's PyTorch path
 // takes it.  `out`: a [M, N] bf16 view to write into (last stride 1, any row stride) instead of a new tensor.
+//
+// ln_gamma / ln_beta [K] in x's dtype with ln_eps: every row of x is LayerNormed before the product; residual [M, N]
+// in x's dtype (last stride 1, any row stride) is added after act, before the one rounding (csrc/linear_rows_fused.hip,
+// one launch).  With neither the call is the plain kernel's.  `out` may then overlap neither residual nor x: raises.
 static c10::optional<at::Tensor> linear_rows(const at::Tensor& x, const at::Tensor& weight,
                                              c10::optional<at::Tensor> bias, int64_t act,
-                                             c10::optional<at::Tensor> out) {
+                                             c10::optional<at::Tensor> out, c10::optional<at::Tensor> ln_gamma,
+                                             c10::optional<at::Tensor> ln_beta, double ln_eps,
+                                             c10::optional<at::Tensor> residual) {
   TORCH_CHECK(x.dim() == 2 && weight.dim() == 2, "linear_rows: x [M, K], weight [N, K]");
   const int64_t M = x.size(0), K = x.size(1), N = weight.size(0);
   TORCH_CHECK(weight.size(1) == K, "linear_rows: x [M, ", K, "] and weight [N, ", weight.size(1), "] do not agree");
@@ -350,10 +356,47 @@ static c10::optional<at::Tensor> linear_rows(const at::Tensor& x, const at::Tens
   if (has(out))
     TORCH_CHECK(out->dim() == 2 && out->size(0) == M && out->size(1) == N && out->scalar_type() == x.scalar_type(),
                 "linear_rows: out must be [M, N] in x's dtype");
+  const bool ln = has(ln_gamma) || has(ln_beta), fused = ln || has(residual);
+  if (ln) {
+    TORCH_CHECK(has(ln_gamma) && has(ln_beta), "linear_rows: ln needs both gamma and beta");
+    TORCH_CHECK(ln_gamma->dim() == 1 && ln_gamma->size(0) == K && ln_beta->dim() == 1 && ln_beta->size(0) == K,
+                "linear_rows: ln gamma and beta must be [K = ", K, "]");
+    TORCH_CHECK(ln_gamma->scalar_type() == x.scalar_type() && ln_beta->scalar_type() == x.scalar_type(),
+                "linear_rows: x, ln gamma and ln beta must have one dtype");
+    TORCH_CHECK(ln_eps >= 0.0, "linear_rows: ln eps must be >= 0");
+  }
+  if (has(residual)) {
+    TORCH_CHECK(residual->dim() == 2 && residual->size(0) == M && residual->size(1) == N,
+                "linear_rows: residual must be [M, N] = [", M, ", ", N, "]");
+    TORCH_CHECK(residual->scalar_type() == x.scalar_type(), "linear_rows: x and residual must have one dtype");
+  }
+  if (fused && has(out)) {
+    auto overlap = [&](const at::Tensor& t) {  // byte ranges from the first to the last element
+      auto span = [](const at::Tensor& u) {
+        const char* lo = static_cast<const char*>(u.data_ptr());
+        int64_t last = 0;
+        for (int64_t d = 0; d < u.dim(); ++d) last += (u.size(d) - 1) * u.stride(d);
+        return std::make_pair(lo, lo + (last + 1) * u.element_size());
+      };
+      if (t.numel() == 0 || out->numel() == 0) return false;
+      const auto a = span(t), b = span(*out);
+      return a.first < b.second && b.first < a.second;
+    };
+    TORCH_CHECK(!overlap(x), "linear_rows: out may not overlap x when ln or residual is given");
+    TORCH_CHECK(!has(residual) || !overlap(*residual), "linear_rows: out may not overlap residual");
+  }
   if (!x.is_cuda() || !weight.is_cuda() || weight.device() != x.device()) return c10::nullopt;
   if (has(bias) && (!bias->is_cuda() || bias->device() != x.device() || !bias->is_contiguous())) return c10::nullopt;
   if (has(out) && (!out->is_cuda() || out->device() != x.device())) return c10::nullopt;
   if (x.scalar_type() != at::kBFloat16 || M < 1 || M > 128 || K < 64 || K % 64) return c10::nullopt;
+  if (ln)
+    for (const at::Tensor* t : {&*ln_gamma, &*ln_beta})
+      if (!t->is_cuda() || t->device() != x.device() || !t->is_contiguous() ||
+          reinterpret_cast<uintptr_t>(t->data_ptr()) % 16)
+        return c10::nullopt;
+  if (has(residual) && (!residual->is_cuda() || residual->device() != x.device() || (N > 1 && residual->stride(1) != 1) ||
+                        (M > 1 && residual->stride(0) < N)))
+    return c10::nullopt;
   auto rows_ok = [&](const at::Tensor& t) {  // last stride 1, 16-byte row starts, rows that do not overlap
     return t.stride(1) == 1 && (t.size(0) == 1 || (t.stride(0) % 8 == 0 && t.stride(0) >= t.size(1))) &&
            reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
@@ -362,9 +405,14 @@ static c10::optional<at::Tensor> linear_rows(const at::Tensor& x, const at::Tens
   if (has(out) && ((N > 1 && out->stride(1) != 1) || (M > 1 && out->stride(0) < N))) return c10::nullopt;
   const c10::DeviceGuard guard(x.device());
   at::Tensor y = has(out) ? *out : at::empty({M, N}, x.options());
-  const bool ok = dpa::launch_linear_rows(bf_ptr(x), M > 1 ? x.stride(0) : K, bf_ptr(weight), N > 1 ? weight.stride(0) : K,
-                                          opt_bf_ptr(bias), bf_mut(y), M > 1 ? y.stride(0) : N, (int)M, N, (int)K,
-                                          (int)act, cur_stream());
+  const int64_t ldx = M > 1 ? x.stride(0) : K, ldw = N > 1 ? weight.stride(0) : K, ldy = M > 1 ? y.stride(0) : N;
+  const bool ok =
+      fused ? dpa::launch_linear_rows_fused(bf_ptr(x), ldx, opt_bf_ptr(ln_gamma), opt_bf_ptr(ln_beta), (float)ln_eps,
+                                            bf_ptr(weight), ldw, opt_bf_ptr(bias), opt_bf_ptr(residual),
+                                            has(residual) && M > 1 ? residual->stride(0) : N, bf_mut(y), ldy, (int)M, N,
+                                            (int)K, (int)act, cur_stream())
+            : dpa::launch_linear_rows(bf_ptr(x), ldx, bf_ptr(weight), ldw, opt_bf_ptr(bias), bf_mut(y), ldy, (int)M, N,
+                                      (int)K, (int)act, cur_stream());
   if (!ok) return c10::nullopt;
   return y;
 }
@@ -417,8 +465,10 @@ void dpa::register_attention(pybind11::module& m) {
         py::arg("x"), py::arg("codes"), py::arg("exps"), py::arg("bias") = py::none(), py::arg("act") = 0,
         py::arg("out") = py::none());
   m.def("linear_rows", &linear_rows,
-        "a decode step's Linear: x [M <= 128, K % 64 == 0] bf16 against weight [N, K] bf16 (+ bias [N], act code) -> y [M, N] bf16, each output row a function of its input row alone | None (case not covered)",
-        py::arg("x"), py::arg("weight"), py::arg("bias") = py::none(), py::arg("act") = 0, py::arg("out") = py::none());
+        "a decode step's Linear: x [M <= 128, K % 64 == 0] bf16 against weight [N, K] bf16 (+ bias [N], act code; ln_gamma / ln_beta [K] + ln_eps: LayerNorm of x's rows first; residual [M, N]: added after act) -> y [M, N] bf16, each output row a function of its input row alone | None (case not covered)",
+        py::arg("x"), py::arg("weight"), py::arg("bias") = py::none(), py::arg("act") = 0, py::arg("out") = py::none(),
+        py::arg("ln_gamma") = py::none(), py::arg("ln_beta") = py::none(), py::arg("ln_eps") = 0.0,
+        py::arg("residual") = py::none());
   m.def("attn128_supports", &dpa::attn128_supports, "the persistent L = 128 attention covers (L, D, causal)");
   m.def("attn_fwd", &attn_fwd, "fused attention forward (head_dim 64/128) -> (out, lse)", py::arg("qkv"),
         py::arg("heads"), py::arg("p"), py::arg("causal"), py::arg("seed"), py::arg("offset"),

@@ -313,6 +313,19 @@ int attn_decode_grouped_qs(int64_t BH, int G, int ncu);
 bool launch_linear_rows(const uint16_t* x, int64_t ldx, const uint16_t* W, int64_t ldw, const uint16_t* bias,
                         uint16_t* y, int64_t ldy, int M, int64_t N, int K, int act, hipStream_t s);
 
+// ---- linear_rows_fused.hip: LayerNorm -> Linear (+ act) -> + residual on the same rows (K-M30) ----
+// a[m][k] = bf16((x[m][k] - mean_m) rsqrt(var_m + eps) gamma[k] + beta[k]) with the row's two-pass fp32 mean and
+// variance when gamma / beta [K] bf16 are given (both or neither; 16-byte aligned), a = x otherwise;
+// y[m][n] = bf16(act(sum_k a[m][k] W[n][k] + bias[n]) + res[m][n]) with res [M][N] bf16, rows ldr elements apart,
+// or null.  Everything else as launch_linear_rows, whose row contract extends: the bits of a[m][:] depend on
+// x[m][:], gamma, beta, eps and K alone, those of y[m][n] also on W[n][:], bias[n], act and res[m][n].  y may not
+// overlap x or res (the caller checks).  Nothing at or beyond x[M], W[N], res[M] is loaded.  false, with no launch:
+// what launch_linear_rows declines, neither gamma nor res (that call is launch_linear_rows's), one of gamma and
+// beta alone, ldr < N, gamma or beta not 16-byte aligned, eps negative or NaN.
+bool launch_linear_rows_fused(const uint16_t* x, int64_t ldx, const uint16_t* gamma, const uint16_t* beta, float eps,
+                              const uint16_t* W, int64_t ldw, const uint16_t* bias, const uint16_t* res, int64_t ldr,
+                              uint16_t* y, int64_t ldy, int M, int64_t N, int K, int act, hipStream_t s);
+
 // ---- linear_rows_fp8.hip: the same Linears on one-byte weights, W8A16 (K-M29) ----
 // y[m][n] = bf16(act(ldexp(sum_k x[m][k] float(W8[n][k]), we[n]) + bias[n])): x [M][K] and y [M][N] bf16 with rows
 // ldx and ldy elements apart, W8 [N][K] e4m3fn codes with rows ldw bytes apart, we [N] int8 exponents (the format

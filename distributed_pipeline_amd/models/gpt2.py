@@ -95,16 +95,17 @@ class GPT2LMModel(nn.Module):
 
     def _rows(self, decode_linears, n_rows, ref):
         """How a call of ``n_rows`` rows on ``ref``'s device runs its Linears: "rows" (through
-        ``ops.decode.linear_rows``: asked for, at most 128 rows, bf16 compute on a HIP device), "rows_fp8"
+        ``ops.decode.linear_rows``: asked for, at most 128 rows, bf16 compute on a HIP device), "rows_fused" (the
+        same op with each block's LayerNorms and residual adds inside it, under the same conditions), "rows_fp8"
         (through ``ops.decode.linear_rows_fp8`` on the quantized snapshot: wherever it is asked for) or False
         (``ops.linear``)."""
-        if decode_linears not in ("tile", "rows", "rows_fp8"):
-            raise ValueError(f"decode_linears must be 'tile', 'rows' or 'rows_fp8', got {decode_linears!r}")
+        if decode_linears not in ("tile", "rows", "rows_fp8", "rows_fused"):
+            raise ValueError(f"decode_linears must be 'tile', 'rows', 'rows_fp8' or 'rows_fused', got {decode_linears!r}")
         if decode_linears == "rows_fp8":
             return "rows_fp8"
         from ..ops.decode import ROWS_MAX_M
-        return (decode_linears == "rows" and n_rows <= ROWS_MAX_M and ref.is_cuda
-                and self.compute_dtype == torch.bfloat16) and "rows"
+        return (decode_linears != "tile" and n_rows <= ROWS_MAX_M and ref.is_cuda
+                and self.compute_dtype == torch.bfloat16) and decode_linears
 
     @torch.no_grad()
     def quantize_decode_weights(self):
@@ -128,16 +129,22 @@ class GPT2LMModel(nn.Module):
             self.quantize_decode_weights()
         return self._decode_w8[id(weight)]
 
-    def _lin_rows(self, lin, t, rows="rows"):
+    def _lin_rows(self, lin, t, rows="rows", ln=None, residual=None):
         """``lin(t)`` for a ``layers.Linear`` through ``ops.decode.linear_rows`` on the bf16 shadows, or with
-        ``rows="rows_fp8"`` through ``ops.decode.linear_rows_fp8`` on the snapshot (the bias stays as it is)."""
+        ``rows="rows_fp8"`` through ``ops.decode.linear_rows_fp8`` on the snapshot (the bias stays as it is).
+        ``ln``: a ``layers.LayerNorm`` applied to ``t`` inside the call; ``residual``: added to the result inside it
+        (``linear_rows``'s keywords, "rows_fused")."""
         from ..ops.decode import linear_rows, linear_rows_fp8
         dt = self.compute_dtype
         t2 = t.reshape(-1, t.shape[-1])
         if rows == "rows_fp8":
             y = linear_rows_fp8(t2, *self._w8(lin.weight), ops.shadow(lin.bias, dt), act=lin.act)
-        else:
+        elif ln is None and residual is None:
             y = linear_rows(t2, ops.shadow(lin.weight, dt), ops.shadow(lin.bias, dt), act=lin.act)
+        else:
+            y = linear_rows(t2, ops.shadow(lin.weight, dt), ops.shadow(lin.bias, dt), act=lin.act,
+                            ln=None if ln is None else (ops.shadow(ln.weight, dt), ops.shadow(ln.bias, dt), ln.eps),
+                            residual=None if residual is None else residual.reshape(-1, residual.shape[-1]))
         return y.view(*t.shape[:-1], -1)
 
     def _head(self, a, rows):
@@ -154,7 +161,17 @@ class GPT2LMModel(nn.Module):
         """The block stack of ``hidden_states`` in eval mode with ``attend(i, qkv)`` as layer i's
         attention over its packed projection -> ln_f of the last residual stream.  ``rows``: the four
         Linears of every block run through ``ops.decode.linear_rows`` or, for "rows_fp8",
-        ``ops.decode.linear_rows_fp8`` (:meth:`_rows` says which)."""
+        ``ops.decode.linear_rows_fp8`` (:meth:`_rows` says which).  "rows_fused": ``a`` is not used - ln_1 and ln_2
+        run inside qkv and mlp_fc and the two residual adds inside attn_proj and mlp_proj (five launches per block
+        instead of seven); ln_f is ``ops.layer_norm``, one launch per call."""
+        if rows == "rows_fused":
+            # five launches per block: only the residual stream x is carried, each LayerNorm runs in the prologue
+            # of the Linear that reads it and each residual add in the epilogue of the Linear in front of it
+            for i, blk in enumerate(self.h):
+                qkv = self._lin_rows(blk.attn.qkv, x, rows, ln=blk.ln_1)
+                x = self._lin_rows(blk.attn_proj, attend(i, qkv), rows, residual=x)
+                x = self._lin_rows(blk.mlp_proj, self._lin_rows(blk.mlp_fc, x, rows, ln=blk.ln_2), rows, residual=x)
+            return ops.layer_norm(x, self.ln_f.weight, self.ln_f.bias, self.ln_f.eps)
         lns = [blk.ln_1 for blk in self.h] + [self.ln_f]
         for i, blk in enumerate(self.h):
             if rows:
@@ -293,7 +310,12 @@ class GPT2LMModel(nn.Module):
         first use; it does not follow later weight updates) - on any device and at any row count, the op's
         PyTorch definition serving what its kernel does not, so the mode means the same numbers everywhere.
         The embedding lookup reads ``wte`` unquantized and the biases stay as they are.  The residual adds,
-        the LayerNorms and the attention are the same in all three.  The modes round differently."""
+        the LayerNorms and the attention are the same in all three.  "rows_fused" is "rows" (same conditions, "tile"
+        anywhere else) with each block's two LayerNorms and two residual adds inside ``linear_rows`` (its ``ln`` and
+        ``residual`` keywords): LN1 + qkv, attention, attn_proj + residual, LN2 + mlp_fc + GELU, mlp_proj + residual -
+        five launches per block instead of seven; ln_f is one ``ops.layer_norm`` launch and the head is
+        ``linear_rows``.  There the residual stream is rounded to bf16 once per sublayer (the sum, not the branch and
+        then the sum).  The modes round differently."""
         from ..ops.decode import attention_decode, attention_decode_fp8
         if isinstance(cache, GroupKVCache):
             if table is not None:
@@ -343,7 +365,7 @@ class GPT2LMModel(nn.Module):
         ``cache``: one from :meth:`init_cache` to use (default: a new one of just the size needed).
         ``kv_dtype``: "bf16" or "fp8" - the one-byte cache, half the bytes per cached token - for
         the new cache (default "bf16"); given together with a ``cache`` of the other kind it is an
-        error.  ``decode_linears``: "tile", "rows" or "rows_fp8", handed to :meth:`prefill` and every
+        error.  ``decode_linears``: "tile", "rows", "rows_fp8" or "rows_fused", handed to :meth:`prefill` and every
         :meth:`decode_step`.  ``prefill_chunk``: :meth:`prefill`'s ``chunk`` (0: the single forward).
         The loop runs on the device; the host looks at it once every ``check_every`` steps (0:
         never), to stop early when every row has finished.
@@ -660,7 +682,7 @@ class GPT2LMModel(nn.Module):
         max_draft) -> (draft [B, max_draft], k [B])`` to use instead - ``history[b, :n[b]]`` is the
         row's prompt and output so far.  ``return_stats`` adds a dict: ``model_calls`` (iterations with
         a live row), ``proposed`` and ``accepted`` guesses, read back once at the end.
-        ``decode_linears``: "tile", "rows" or "rows_fp8", handed to :meth:`prefill` and every :meth:`decode_block`.
+        ``decode_linears``: "tile", "rows", "rows_fp8" or "rows_fused", handed to :meth:`prefill` and every :meth:`decode_block`.
 
         The logit processors of :meth:`generate` are not available here: the guesses continue
         repeated n-grams, which is what those penalties forbid, and the queries of a block would
@@ -781,7 +803,7 @@ class GPT2LMModel(nn.Module):
         logits are one row per prompt repeated for every beam, so they are penalised once, before
         they are expanded.  The scores are sums of the log-softmax of the processed logits.
 
-        ``decode_linears``: "tile", "rows" or "rows_fp8", handed to :meth:`prefill` and every :meth:`decode_step`
+        ``decode_linears``: "tile", "rows", "rows_fp8" or "rows_fused", handed to :meth:`prefill` and every :meth:`decode_step`
         (``B W`` rows)."""
         from ..ops.decode import beam_step, penalize_logits_
         penalties, min_new = _logit_processors(repetition_penalty, presence_penalty, frequency_penalty,

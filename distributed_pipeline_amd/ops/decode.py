@@ -297,7 +297,8 @@ the two integers are exact on both.
 
 The Linears of a decode step: ``linear_rows``
 ---------------------------------------------
-``linear_rows(x [M, K], weight [N, K], bias [N] | None = None, *, act="none") -> y [M, N]`` in ``x``'s dtype:
+``linear_rows(x [M, K], weight [N, K], bias [N] | None = None, *, act="none", ln=None, residual=None) -> y [M, N]``
+in ``x``'s dtype; without the last two keywords (they are defined below):
 
 * ``y[m, n] = round_to_dtype(act(sum_k x[m, k] * W[n, k] + b[n]))``: products and the sum in fp32, the
   bias added in fp32, ``act`` ("none", "gelu", "tanh", "silu": the codes and functions of csrc/act.h)
@@ -318,6 +319,24 @@ K, such as a row slice of a larger matrix, is served); ``bias`` bf16 or absent: 
 csrc/linear_rows.hip.  Anything else (CPU, fp32, a larger M, another K): :func:`linear_rows_ref`, the
 definition in fp32 PyTorch (its GELU is the exact one; the kernel's is ``gelu_f``, below bf16 resolution
 of it).
+
+A whole sublayer in one call: ``linear_rows(x, weight, bias, *, act, ln=(gamma [K], beta [K], eps), residual [M, N])``.
+``ln`` normalises every row of ``x`` before the product, ``residual`` (in ``x``'s dtype) is added after ``act``.
+All arithmetic is fp32::
+
+    mean_m = (sum_k x[m,k]) / K
+    var_m  = (sum_k (x[m,k] - mean_m)^2) / K        # two passes over the row; not E[x^2] - mean^2
+    a[m,k] = bf16((x[m,k] - mean_m) * rsqrt(var_m + eps) * gamma[k] + beta[k])   # the B operand, rounded once
+    y[m,n] = bf16(act(sum_k a[m,k] * W[n,k] + b[n]) + residual[m,n])             # one rounding
+
+Without ``ln``, ``a = x``; with neither keyword the call is the one above, bit for bit, through the same kernel
+instantiations.  ``gamma`` and ``beta`` are what ``ops.residual_layernorm`` hands its kernel: the compute-dtype
+(bf16) shadows of the LayerNorm's parameters.  The kernel path is csrc/linear_rows_fused.hip (one launch, the same
+envelope as above; ``residual`` with last stride 1 and any row stride), and the row contract extends: the bits of
+``a[m, :]`` are a function of ``x[m, :]``, ``gamma``, ``beta``, ``eps`` and K alone, the bits of ``y[m, n]``
+additionally of ``W[n, :]``, ``b[n]``, ``act`` and ``residual[m, n]`` - not of M, of the row's place, of N for
+``a``, of the other rows or of the grid.  :func:`linear_rows_ref` takes the same keywords, rounds ``a`` the same way
+and serves everything the kernel declines.  ``linear_rows_fp8`` has no such keywords.
 
 The same Linears on one-byte weights: ``linear_rows_fp8``
 ---------------------------------------------------------
@@ -1155,40 +1174,65 @@ ROWS_MAX_M = 128  # the most rows csrc/linear_rows.hip takes
 _ROWS_ACTS = {"none": 0, "gelu": 1, "tanh": 2, "silu": 3}  # csrc/act.h
 
 
-def _check_linear_rows(x, weight, bias, act):
+def _check_linear_rows(x, weight, bias, act, ln=None, residual=None):
     if act not in _ROWS_ACTS:
         raise ValueError(f"act must be one of {sorted(_ROWS_ACTS)}, got {act!r}")
     if x.dim() != 2 or weight.dim() != 2 or weight.shape[1] != x.shape[1] or weight.shape[0] < 1:
         raise ValueError(f"x must be [M, K] and weight [N >= 1, K], got {tuple(x.shape)}, {tuple(weight.shape)}")
     if bias is not None and tuple(bias.shape) != (weight.shape[0],):
         raise ValueError(f"bias must be [{weight.shape[0]}], got {tuple(bias.shape)}")
+    if ln is not None:
+        gamma, beta, eps = ln
+        if tuple(gamma.shape) != (x.shape[1],) or tuple(beta.shape) != (x.shape[1],) or not float(eps) >= 0.0:
+            raise ValueError(f"ln must be (gamma [{x.shape[1]}], beta [{x.shape[1]}], eps >= 0), got "
+                             f"{tuple(gamma.shape)}, {tuple(beta.shape)}, {eps!r}")
+    if residual is not None and (tuple(residual.shape) != (x.shape[0], weight.shape[0]) or residual.dtype != x.dtype):
+        raise ValueError(f"residual must be {x.dtype} [{x.shape[0]}, {weight.shape[0]}], got {residual.dtype} "
+                         f"{tuple(residual.shape)}")
 
 
-def linear_rows_ref(x, weight, bias=None, *, act="none"):
+def linear_rows_ref(x, weight, bias=None, *, act="none", ln=None, residual=None):
     """The definition in fp32 PyTorch (any device, any float dtype) -> y [M, N] in ``x``'s dtype."""
-    _check_linear_rows(x, weight, bias, act)
-    z = F.linear(x.detach().float(), weight.detach().float(), None if bias is None else bias.detach().float())
+    _check_linear_rows(x, weight, bias, act, ln, residual)
+    a = x.detach().float()
+    if ln is not None:
+        gamma, beta, eps = ln
+        d = a - a.mean(-1, keepdim=True)
+        rstd = torch.rsqrt((d * d).mean(-1, keepdim=True) + float(eps))
+        a = (d * rstd * gamma.detach().float() + beta.detach().float()).to(x.dtype).float()  # the B operand, rounded once
+    z = F.linear(a, weight.detach().float(), None if bias is None else bias.detach().float())
     z = {"none": lambda t: t, "gelu": F.gelu, "tanh": torch.tanh, "silu": F.silu}[act](z)
+    if residual is not None:
+        z = z + residual.detach().float()
     return z.to(x.dtype)
 
 
 @torch.no_grad()
-def linear_rows(x, weight, bias=None, *, act="none"):
-    """-> y [M, N] = act(x W^T + b) in ``x``'s dtype, each output row a function of its input row alone:
-    the module docstring has the definition and the row contract."""
-    _check_linear_rows(x, weight, bias, act)
+def linear_rows(x, weight, bias=None, *, act="none", ln=None, residual=None):
+    """-> y [M, N] = act(LN(x) W^T + b) + residual in ``x``'s dtype, each output row a function of its input row
+    (and its residual row) alone: the module docstring has the definition and the row contract.  ``ln``: a tuple
+    ``(gamma [K], beta [K], eps)`` or None (no LayerNorm); ``residual`` [M, N] in ``x``'s dtype or None."""
+    _check_linear_rows(x, weight, bias, act, ln, residual)
     if x.shape[0] == 0:
         return x.new_empty(0, weight.shape[0])
     if x.is_cuda:
         ext = get_ext()  # raises on a GPU without the built extension: no quiet fall-back
         if ext is not None and x.dtype == torch.bfloat16 and weight.dtype == x.dtype and (
-                bias is None or bias.dtype == x.dtype):
+                bias is None or bias.dtype == x.dtype) and (ln is None or ln[0].dtype == ln[1].dtype == x.dtype):
             if x.stride(-1) != 1 or x.stride(0) % 8 or x.data_ptr() % 16:
                 x = x.contiguous()
-            out = ext.linear_rows(x, weight, None if bias is None else bias.contiguous(), _ROWS_ACTS[act])
+            args = (x, weight, None if bias is None else bias.contiguous(), _ROWS_ACTS[act])
+            if ln is None and residual is None:
+                out = ext.linear_rows(*args)  # the call, and the kernel instantiations, of before the keywords
+            else:
+                lnk = {} if ln is None else {"ln_gamma": ln[0].contiguous(), "ln_beta": ln[1].contiguous(),
+                                             "ln_eps": float(ln[2])}
+                if residual is not None and residual.stride(-1) != 1:
+                    residual = residual.contiguous()
+                out = ext.linear_rows(*args, residual=residual, **lnk)
             if out is not None:
                 return out
-    return linear_rows_ref(x, weight, bias, act=act)
+    return linear_rows_ref(x, weight, bias, act=act, ln=ln, residual=residual)
 
 
 # ---- linear_rows_fp8 ----------------------------------------------------------------------------

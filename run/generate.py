@@ -68,6 +68,11 @@ such weight and the tied ``wte`` are quantized once to e4m3fn codes with one pow
 (``--kv_dtype fp8``'s format) and the steps run ``ops.decode.linear_rows_fp8``, which reads half the bytes.  The
 embedding lookup, the biases and the prompt's own forward keep the bf16 weights.  The mode means the same numbers
 on any device and at any row count: where the kernel does not apply, its PyTorch definition runs.
+
+``--decode_linears rows_fused`` is ``rows`` with each block's two LayerNorms and two residual adds inside the row
+kernel (``ops.decode.linear_rows``'s ``ln`` and ``residual`` keywords): five launches per block instead of seven.
+It applies where ``rows`` does and is ``tile`` anywhere else; the residual stream is rounded once per sublayer, so
+continuations can differ from the other modes'.
 """
 import json
 import os

@@ -5,15 +5,22 @@ bandwidth yardstick - all in one process and interleaved.  Beside them the same 
 (csrc/linear_rows_fp8.hip through ``ext.linear_rows_fp8``, the weights quantized with ``kv_quantize_ref``) and a
 device copy of the fp8 weight's bytes, on weight copies of their own spread over the same number of bytes.
 
-    python tools/decode_linear_bench.py [--M 1,8,64,128] [--reps 7] [--spread_mb 768] [--no_model] [--out FILE]
+    python tools/decode_linear_bench.py [--M 1,8,64,128] [--reps 7] [--spread_mb 768] [--no_linears] [--no_model]
+                                        [--out FILE]
 
 Shapes: GPT-2 small's five Linears, (N, K) = qkv (2304, 768), attn_proj (768, 768), mlp_fc (3072, 768, GELU),
 mlp_proj (768, 3072) and the tied head (50257, 768, no bias).  Consecutive calls of a variant take
 different copies of the weight, so that ``spread_mb`` of reads pass before one repeats and nothing is
 served from the last-level cache.
 
+The fused sublayers (csrc/linear_rows_fused.hip, ``ext.linear_rows`` with ``ln_*`` / ``residual``) are timed as the
+two chains of a block, "rows" against "rows_fused" on the same rotating weights: ``ln_qkv`` (rows: the
+``residual_layernorm`` launch and the qkv launch; fused: one launch) and ``proj_ln_fc`` (rows: attn_proj,
+``residual_layernorm``, mlp_fc; fused: attn_proj + residual, LN + mlp_fc).  ``--no_linears`` skips the single Linears.
+
 It also times one whole ``GPT2LMModel.decode_step`` at (B, len) = (64, 512) and (8, 512) with
-``decode_linears="tile"``, ``"rows"`` and ``"rows_fp8"``, interleaved in the same run (``--no_model`` skips it).
+``decode_linears="tile"``, ``"rows"``, ``"rows_fp8"`` and ``"rows_fused"``, interleaved in the same run (``--no_model``
+skips it).
 
 Every variant of a shape is timed in turn inside each repetition; a repetition is ``inner`` back-to-back
 calls between two device events; medians and min-max over the repetitions.
@@ -93,6 +100,51 @@ def shape(name, N, K, act, has_bias, M, reps, spread_bytes):
     return {"linear": name, "M": M, "N": N, "K": K, "act": act, "weight_bytes": nbytes, "weight_copies": nsets, **out}
 
 
+def sublayers(M, reps, spread_bytes, H=768):
+    """The two chains of a GPT-2 small block at M rows, "rows" against "rows_fused", interleaved."""
+    from distributed_pipeline_amd.ops import nn
+    from distributed_pipeline_amd.ops._ext import get_ext
+    ext = get_ext(required=True)
+    g = torch.Generator(device="cuda").manual_seed(0)
+    rnd = lambda *sh: torch.randn(*sh, device="cuda", generator=g).bfloat16()  # noqa: E731
+    sets = lambda N, K: [torch.empty(N, K, device="cuda", dtype=torch.bfloat16).normal_(0.0, K ** -0.5, generator=g)  # noqa: E731
+                         for _ in range(max(1, -(-spread_bytes // (N * K * 2))))]
+    wq, wp, wf = sets(3 * H, H), sets(H, H), sets(4 * H, H)
+    bq, bp, bf = rnd(3 * H), rnd(H), rnd(4 * H)
+    x, h, gm, bt = rnd(M, H), rnd(M, H), rnd(H), rnd(H)
+    turn = {}
+
+    def nxt(key, ws):
+        turn[key] = (turn.get(key, -1) + 1) % len(ws)
+        return ws[turn[key]]
+
+    def ln_qkv_rows():
+        _, a = nn.residual_layernorm(h.view(1, M, H), x.view(1, M, H), gm, bt, 0.0, 1e-5, False)
+        return ext.linear_rows(a.view(M, H), nxt("q0", wq), bq, 0)
+
+    def ln_qkv_fused():
+        return ext.linear_rows(x, nxt("q1", wq), bq, 0, ln_gamma=gm, ln_beta=bt, ln_eps=1e-5)
+
+    def proj_ln_fc_rows():
+        y = ext.linear_rows(h, nxt("p0", wp), bp, 0)
+        _, a = nn.residual_layernorm(y.view(1, M, H), x.view(1, M, H), gm, bt, 0.0, 1e-5, False)
+        return ext.linear_rows(a.view(M, H), nxt("f0", wf), bf, 1)
+
+    def proj_ln_fc_fused():
+        x2 = ext.linear_rows(h, nxt("p1", wp), bp, 0, residual=x)
+        return ext.linear_rows(x2, nxt("f1", wf), bf, 1, ln_gamma=gm, ln_beta=bt, ln_eps=1e-5)
+
+    with torch.no_grad():
+        assert ln_qkv_fused() is not None and proj_ln_fc_fused() is not None, "the fused kernel must take this shape"
+        out = interleaved({"ln_qkv_rows": (ln_qkv_rows, 300), "ln_qkv_fused": (ln_qkv_fused, 300),
+                           "proj_ln_fc_rows": (proj_ln_fc_rows, 200), "proj_ln_fc_fused": (proj_ln_fc_fused, 200)}, reps)
+    for chain in ("ln_qkv", "proj_ln_fc"):
+        r, f = out[chain + "_rows"], out[chain + "_fused"]
+        f["speedup_vs_rows"] = round(r["median_ms"] / f["median_ms"], 2)
+        f["ranges_overlap_rows"] = bool(f["max_ms"] >= r["min_ms"] and r["max_ms"] >= f["min_ms"])
+    return {"sublayers": "gpt2", "M": M, **out}
+
+
 def model_steps(shapes, reps):
     from distributed_pipeline_amd.models import build_model
     torch.manual_seed(0)
@@ -118,9 +170,13 @@ def model_steps(shapes, reps):
         alone = model.decode_step(ids[:1, n - 1], one, decode_linears="rows")
         same = bool(torch.equal(alone.view(torch.int16), step("rows")[:1].view(torch.int16)))
         out = interleaved({"tile": (lambda: step("tile"), 20), "rows": (lambda: step("rows"), 20),
-                           "rows_fp8": (lambda: step("rows_fp8"), 20)}, reps, warmup=2)
+                           "rows_fp8": (lambda: step("rows_fp8"), 20),
+                           "rows_fused": (lambda: step("rows_fused"), 20)}, reps, warmup=2)
         out["rows"]["speedup_vs_tile"] = round(out["tile"]["median_ms"] / out["rows"]["median_ms"], 2)
         out["rows_fp8"]["speedup_vs_rows"] = round(out["rows"]["median_ms"] / out["rows_fp8"]["median_ms"], 2)
+        r, f = out["rows"], out["rows_fused"]
+        f["speedup_vs_rows"] = round(r["median_ms"] / f["median_ms"], 2)
+        f["ranges_overlap_rows"] = bool(f["max_ms"] >= r["min_ms"] and r["max_ms"] >= f["min_ms"])
         res.append({"model": "gpt2", "B": B, "len": n, "row_0_alone_bit_equal_rows_mode": same, **out})
     return res
 
@@ -130,12 +186,16 @@ def main():
     ap.add_argument("--M", default="1,8,64,128")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--spread_mb", type=int, default=768, help="weight bytes read before a copy is reused, MB")
+    ap.add_argument("--no_linears", action="store_true", help="skip the single Linears (the fused chains still run)")
     ap.add_argument("--no_model", action="store_true")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a HIP device"
     lines = [json.dumps({"device": torch.cuda.get_device_name(0), "reps": a.reps, "torch": torch.__version__})]
-    for name, N, K, act, has_bias in LINEARS:
+    for M in (int(v) for v in a.M.split(",")):
+        lines.append(json.dumps(sublayers(M, a.reps, a.spread_mb << 20)))
+        print(lines[-1], flush=True)
+    for name, N, K, act, has_bias in ([] if a.no_linears else LINEARS):
         for M in (int(v) for v in a.M.split(",")):
             lines.append(json.dumps(shape(name, N, K, act, has_bias, M, a.reps, a.spread_mb << 20)))
             print(lines[-1], flush=True)
